@@ -15,10 +15,20 @@ backward + AdamW.  One process per GPU; data parallel by scene (one scene per ra
 gradients averaged over RCCL (backend "nccl" on ROCm) by one flat all-reduce per step (or torch DDP,
 AO_AMD_GRAD_SYNC=ddp).  Rank 0 prints ONE JSON line.
 
-Extra objects on that line (task section 4):
-  roofline      the dominant hand-written kernel, timed live with HIP events on the launch stream
-  cpu_baseline  the CPU oracle (oracle/ptv2_ref.py + C kNN) timed on this box's host cores on a
-                bounded sample of the same workload (rank 0, N=1 only)
+A plain run sets up, warms up, times the K steps and prints the line (headline `value` / `ms_per_step` plus the `host` and
+`config` objects of the timed region).  `--full` adds everything that takes runs of its own:
+  roofline         the dominant hand-written kernel, timed live with HIP events on the launch stream
+  reference_loop   the reference trainer's run_step statements over this build
+  config.also      the reference recipe's per-GPU batch (3 x 80 000 points), timed by a child run
+  ops              kNN / FPS us per query on the run's scene
+  cpu_baseline     the CPU oracle (oracle/ptv2_ref.py + C kNN) timed on this box's host cores on a
+                   bounded sample of the same workload (rank 0, N=1 only)
+(the --no-* options switch single legs of --full off).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (float32):
+`loss`, `logits` (the backbone's output), `params` (after the optimizer step), `grads`, `buffers` (BatchNorm running
+statistics); an array of more than DUMP_CAP elements is written as a fixed, seeded sample of its rows.  The inputs
+(scene, weights, dropout stream) follow from the arguments alone, so two builds can be compared output for output.
 
 Environment switches for boxes with fewer GPUs than ranks (tests/test_gpu_bench_spawn.py):
   AO_AMD_BENCH_BACKEND=gloo      exchange gradients over gloo instead of RCCL (RCCL refuses two ranks on one device)
@@ -66,6 +76,10 @@ def parse():
                     help="backbone config: the headline S3DIS one, or configs/scannet/semseg-pt-v2m2-0-base.py (BASELINE.json configs[4])")
     ap.add_argument("--segmentor", default="default", choices=["default", "sam_image"],
                     help="sam_image: DefaultSegmentorSAM_Image + the per-step logit basket of train_real (BASELINE.json configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: roofline, reference_loop, config.also, ops, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-sample-points", type=int, default=120000,
                     help="points of the CPU-oracle scene (default: the metric's own 120 000; ~1-2 min on the box's 16-CPU quota)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -77,7 +91,35 @@ def parse():
                     help="skip config.also: the reference recipe's per-GPU batch (3 x 80 000 points) timed by a child run")
     ap.add_argument("--spawn-timeout", type=float, default=1800.0,
                     help="--gpus N without a launcher: seconds after which the remaining ranks are terminated (exit 124)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: only the headline's own timed region
+        args.no_cpu_baseline = args.no_roofline = args.no_ops = args.no_reference_loop = args.no_also = True
+    return args
+
+
+DUMP_CAP = 4 << 20  # elements per dumped array (16 MB of float32); five arrays stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array of `arrays` ({name: tensor or ndarray}) as out_dir/<name>.npy in float32.  One with more than DUMP_CAP
+    elements is written as a sample of its rows (of its elements when 1-D): numpy's default_rng(0) over the row count, sorted,
+    so that the same shape always keeps the same rows.  Returns {name: (shape written, full shape)}."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().float().cpu().numpy()
+        a = np.asarray(a, dtype=np.float32)
+        full = a.shape
+        if a.size > DUMP_CAP:
+            per_row = a.size // a.shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_CAP // per_row, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = (list(a.shape), list(full))
+    return written
 
 
 def make_batch(rank, scenes, points, device, in_channels=6, num_classes=13):
@@ -856,13 +898,19 @@ def child_main(args):
     # event per step on the compute stream so that the per-step GPU-side durations can be told apart from host stalls
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     host_wall, host_cpu, reserved_trace = [], [], []
+    captured = {}  # --dump-outputs: the backbone's output of the last timed step, copied (a runtime buffer may be reused)
 
     def timed_step():
         i = len(host_wall)
         if i == 0:
             marks[0].record()
+        hook = None
+        if args.dump_outputs and i == args.steps - 1:
+            hook = seg.backbone.register_forward_hook(lambda m, a, y: captured.update(logits=y.detach().float().clone()))
         w0, c0 = time.perf_counter(), time.thread_time()
         out = step()
+        if hook is not None:
+            hook.remove()
         host_wall.append(time.perf_counter() - w0)
         host_cpu.append(time.thread_time() - c0)
         reserved_trace.append(torch.cuda.memory_reserved(device))
@@ -898,6 +946,14 @@ def child_main(args):
         dist.all_gather_object(per_rank, mine)
     if prefetch is not None:
         prefetch.close()  # (thread mode: the geometry of the batch after the last one is still being built)
+    if args.dump_outputs and rank == 0:
+        params = list(seg.parameters())
+        written = dump_outputs(args.dump_outputs, {
+            "loss": loss.detach().reshape(1), "logits": captured["logits"],
+            "params": torch.cat([p.detach().reshape(-1) for p in params]),
+            "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params]),
+            "buffers": torch.cat([b.detach().float().reshape(-1) for b in seg.buffers()])})
+        sys.stderr.write("bench.py: outputs of the last timed step in %s: %s\n" % (args.dump_outputs, json.dumps(written)))
     if not args.no_roofline:
         _lib.lib().ptv2_profile_enable(0)
     ref_loop = None

@@ -26,7 +26,7 @@ def _bench(args, **env):
 
 
 def test_two_ranks_spawned_by_bench_py_on_one_device():
-    common = ["--steps", "3", "--warmup", "2", "--points", "20000", "--no-cpu-baseline", "--no-ops", "--no-roofline"]
+    common = ["--steps", "3", "--warmup", "2", "--points", "20000", "--full", "--no-cpu-baseline", "--no-ops", "--no-roofline"]
     two = _bench(["--gpus", "2"] + common, AO_AMD_BENCH_ONE_DEVICE="1", AO_AMD_BENCH_BACKEND="gloo")
     # (Round 3 retried here once on a NaN loss, seen once in 67 runs, always the first process group on a fresh box.  Root cause
     # found in round 4 in the ISA: the "last block arrives" protocol of the in-kernel reductions published its arrival without

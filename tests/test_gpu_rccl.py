@@ -19,7 +19,7 @@ def _bench(extra_env, *args):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--points", "30000",
-                          "--no-cpu-baseline", "--no-ops", "--no-roofline", *args], env=env, capture_output=True, text=True,
+                          "--full", "--no-cpu-baseline", "--no-ops", "--no-roofline", *args], env=env, capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -1,51 +1,44 @@
 """CPU: ao_amd.ptv2.registry puts this package's classes under the reference's registry names with the reference's own
 `register_module` idiom, so that `optimizer = dict(type="FlatAdamW", ...)` / `backbone = dict(type="PT-v2m2", ...)` are config
-edits (pointcept/utils/optimizer.py:12-17,55; pointcept/models/builder.py).  Uses the reference's Registry class where the
-reference tree is present (this container), a minimal stand-in with the same two methods otherwise."""
-import importlib
-import os
-import sys
-import types
+edits (pointcept/utils/optimizer.py:12-17,55; pointcept/models/builder.py).  The registry below is a stand-in with the
+behaviour of the reference's `Registry` that registration relies on: keyword `register_module(name, force, module)` taking
+classes only and a bool `force`, a taken name refused unless `force`, and `build(cfg)` constructing `cfg["type"]` with the
+remaining keys."""
+import inspect
 
+import pytest
 import torch
 
-REF_REGISTRY = "/root/reference/pointcept/utils/registry.py"
 
+class Registry:
+    def __init__(self, name):
+        self.name, self._d = name, {}
 
-def _registry_class():
-    if os.path.exists(REF_REGISTRY):
-        try:  # registry.py imports `.misc`: give the directory a package name of its own (pointcept itself is not importable here)
-            pkg = types.ModuleType("_ref_pointcept_utils")
-            pkg.__path__ = [os.path.dirname(REF_REGISTRY)]
-            sys.modules.setdefault("_ref_pointcept_utils", pkg)
-            return importlib.import_module("_ref_pointcept_utils.registry").Registry
-        except ImportError:
-            pass
+    def register_module(self, name=None, force=False, module=None):
+        if not isinstance(force, bool):
+            raise TypeError("force must be a bool, got %r" % type(force))
+        if not inspect.isclass(module):
+            raise TypeError("module must be a class, got %r" % type(module))
+        name = module.__name__ if name is None else name
+        if not force and name in self._d:
+            raise KeyError("%s is already registered in %s" % (name, self.name))
+        self._d[name] = module
+        return module
 
-    class Registry:  # register_module(name, force, module) / build(cfg): the two calls the reference makes
-        def __init__(self, name):
-            self.name, self._d = name, {}
+    def get(self, key):
+        return self._d.get(key)
 
-        def register_module(self, name=None, force=False, module=None):
-            if not force and name in self._d:
-                raise KeyError(name)
-            self._d[name] = module
-            return module
-
-        def get(self, key):
-            return self._d.get(key)
-
-        def build(self, cfg):
-            args = dict(cfg)
-            return self._d[args.pop("type")](**args)
-
-    return Registry
+    def build(self, cfg):
+        args = dict(cfg)
+        kind = args.pop("type")
+        if kind not in self._d:
+            raise KeyError("%s is not in the %s registry" % (kind, self.name))
+        return self._d[kind](**args)
 
 
 def test_flat_adamw_builds_from_the_optimizer_config_line():
     from ao_amd.ptv2 import registry
 
-    Registry = _registry_class()
     OPTIMIZERS, MODELS = Registry("optimizers"), Registry("models")
     OPTIMIZERS.register_module(module=torch.optim.AdamW, name="AdamW")  # pointcept/utils/optimizer.py:17
     done = registry.register(MODELS=MODELS, OPTIMIZERS=OPTIMIZERS)
@@ -66,3 +59,5 @@ def test_flat_adamw_builds_from_the_optimizer_config_line():
     assert sched.get_last_lr() == [0.006]
     # registering twice (an edited file re-imported) replaces the entry instead of raising
     registry.register(OPTIMIZERS=OPTIMIZERS)
+    with pytest.raises(KeyError):  # without force a taken name is refused, as by the reference's Registry
+        registry.register(OPTIMIZERS=OPTIMIZERS, force=False)

@@ -1,15 +1,15 @@
-# usage: bash tools/gpu/fresh_box.sh TAG [ORDER]   -- one call per fresh box: the default bench line (minus the CPU leg) as the FIRST
+# usage: bash tools/gpu/fresh_box.sh TAG [ORDER] [OUT]   -- one call per fresh box: the --full bench line (minus the CPU leg) as the FIRST
 # process on the box, then eager / graph issue alternately; prints ms per step, the per-step spread and the host figures.
 # ORDER = "g e g" (default) or e.g. "e g e": g = graph issue (default build), e = AO_AMD_GRAPH=0
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-T=$1; ORDER=${2:-"g e g"}
-mkdir -p gpurun_out/fresh
+T=$1; ORDER=${2:-"g e g"}; O=${3:-fresh_box_out}
+mkdir -p $O
 i=0
 for m in $ORDER; do
   i=$((i+1))
   if [ $m = g ]; then E="AO_AMD_GRAPH=1"; else E="AO_AMD_GRAPH=0"; fi
-  env $E python bench.py --no-cpu-baseline --no-ops > gpurun_out/fresh/${T}_${i}${m}.json 2> gpurun_out/fresh/${T}_${i}${m}.err
-  python - gpurun_out/fresh/${T}_${i}${m}.json $m <<'PY'
+  env $E python bench.py --full --no-cpu-baseline --no-ops > $O/${T}_${i}${m}.json 2> $O/${T}_${i}${m}.err
+  python - $O/${T}_${i}${m}.json $m <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -44,14 +44,14 @@ python tools/pmc_sq.py "$O/pmc_sq" > "$O/sq_counters.jsonl" 2> "$O/sq.err"
 rm -rf "$O/pmc_sq"
 # the bench line takes roofline.traffic from the PMC profile of THIS build under profiles/ (matched by source digest)
 cp "$O/pmc_traffic_per_launch.jsonl" profiles/${ROUND:-r06}_final_pmc_traffic_per_launch.jsonl
-python bench.py --steps 30 --warmup 5 > "$O/bench_fp32.json" 2> "$O/bench_fp32.err"
-python bench.py --steps 30 --warmup 5 --dtype bf16 --no-cpu-baseline --no-ops > "$O/bench_bf16.json" 2>/dev/null
-python bench.py --steps 20 --warmup 5 --cfg scannet --scenes 2 --points 100000 --no-cpu-baseline --no-ops > "$O/bench_scannet.json" 2>/dev/null
-python bench.py --steps 20 --warmup 5 --cfg scannet --scenes 2 --points 100000 --dtype bf16 --no-cpu-baseline --no-ops > "$O/bench_scannet_bf16.json" 2>/dev/null
-python bench.py --steps 20 --warmup 5 --segmentor sam_image --no-cpu-baseline --no-ops > "$O/bench_sam.json" 2>/dev/null
-python bench.py --steps 20 --warmup 5 --scenes 4 --points 80000 --no-cpu-baseline --no-ops > "$O/bench_4x80k.json" 2>/dev/null
+python bench.py --full --steps 30 --warmup 5 > "$O/bench_fp32.json" 2> "$O/bench_fp32.err"
+python bench.py --full --steps 30 --warmup 5 --dtype bf16 --no-cpu-baseline --no-ops > "$O/bench_bf16.json" 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --cfg scannet --scenes 2 --points 100000 --no-cpu-baseline --no-ops > "$O/bench_scannet.json" 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --cfg scannet --scenes 2 --points 100000 --dtype bf16 --no-cpu-baseline --no-ops > "$O/bench_scannet_bf16.json" 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --segmentor sam_image --no-cpu-baseline --no-ops > "$O/bench_sam.json" 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --scenes 4 --points 80000 --no-cpu-baseline --no-ops > "$O/bench_4x80k.json" 2>/dev/null
 # the same loop without the prefetcher: the forward builds its own geometry, pipelined with the level-0 prefix
-AO_AMD_PREFETCH=0 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-ops > "$O/bench_fp32_no_prefetcher.json" 2>/dev/null
+AO_AMD_PREFETCH=0 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-ops > "$O/bench_fp32_no_prefetcher.json" 2>/dev/null
 for f in fp32 fp32_no_prefetcher bf16 scannet scannet_bf16 sam 4x80k; do python - "$O/bench_$f.json" "$f" <<'PY'
 import json, sys
 try:
