@@ -75,6 +75,11 @@ _SIGNATURES = {
     "cross_entropy_workspace_bytes": (_c_size, [_c_int]),
     "cross_entropy_forward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 2 + [_c_int] + [_vp] * 5 + [_c_size, _vp]),
     "cross_entropy_backward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 2 + [_c_int] + [_vp] * 5),
+    "lovasz_softmax_workspace_bytes": (_c_size, [_c_int] * 2),
+    "lovasz_softmax_saved_bytes": (_c_size, [_c_int] * 2),
+    "lovasz_softmax_forward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 2 + [_c_int] * 2 + [_vp, ctypes.c_float, _vp, _vp,
+                                                                                               _c_size, _vp, _c_size, _vp]),
+    "lovasz_softmax_backward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 2 + [ctypes.c_float] + [_vp] * 3),
     "bn_stats_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 6 + [ctypes.c_float] * 2 + [_vp, _c_size, _vp]),
     "bn_apply_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 5 + [_c_int, _vp, _vp]),
     "bn_forward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 3 + [_c_int] + [_vp] * 5 + [ctypes.c_float] * 2 + [_vp] * 4

@@ -27,8 +27,10 @@ def _register(registry, cls, name, force):
         registry.register_module(module=cls, name=name)
 
 
-def register(MODELS=None, OPTIMIZERS=None, force=True):
-    """Put PT-v2m2, the two segmentors and FlatAdamW under the reference's registry names.  Either registry may be omitted."""
+def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None):
+    """Put PT-v2m2, the two segmentors and FlatAdamW under the reference's registry names, and with LOSSES
+    (pointcept/models/losses/builder.py) the HIP LovaszLoss under "LovaszLoss": a trainer that keeps the reference's own
+    segmentor and `Criteria` then builds it from the same config entry.  Every registry may be omitted."""
     done = []
     if MODELS is not None:
         from .model import PointTransformerV2
@@ -43,4 +45,9 @@ def register(MODELS=None, OPTIMIZERS=None, force=True):
 
         _register(OPTIMIZERS, FlatAdamW, "FlatAdamW", force)
         done.append("FlatAdamW")
+    if LOSSES is not None:
+        from .losses import LovaszLoss
+
+        _register(LOSSES, LovaszLoss, "LovaszLoss", force)
+        done.append("LovaszLoss")
     return done

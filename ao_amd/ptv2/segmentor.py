@@ -79,26 +79,39 @@ def cross_entropy(logits, label, ignore_index=-1):
 
 
 def _parse_criteria(criteria, ignore_index):
-    """The reference builds `criteria` from a list of loss configs and sums them (pointcept/models/losses/builder.py:
-    13-29).  On this path every config uses ONE CrossEntropyLoss (configs/s3dis/semseg-pt-v2m2-0-base.py:37,
-    semseg-pt-v2m2-0-sam-final.py:37); that is what is implemented: a list of CrossEntropyLoss entries, each with its
-    loss_weight / ignore_index (losses/misc.py:14-39)."""
+    """The reference builds `criteria` from a list of loss configs and sums them in order (pointcept/models/losses/builder.py:
+    13-29).  On this path the configs use CrossEntropyLoss (configs/s3dis/semseg-pt-v2m2-0-base.py:37,
+    semseg-pt-v2m2-0-sam-final.py:37), some followed by LovaszLoss(mode="multiclass") (configs/scannet/semseg-pt-v2m2-3-lovasz.py:
+    37-40, scannet200/semseg-pt-v2m2-2-lovasz.py:43, semantic_kitti/semseg-pt-v2m2-1-benchmark-submit.py:65).  Entries:
+    (loss_weight, ignore_index, None) for CrossEntropyLoss (losses/misc.py:14-39), (loss_weight, ignore_index, LovaszLoss
+    module) for LovaszLoss, whose constructor requires `mode` as the reference's does."""
     if criteria is None:
-        return [(1.0, ignore_index)]
+        return [(1.0, ignore_index, None)]
+    from .losses import LovaszLoss
+
     out = []
     for c in criteria:
         c = dict(c)
         kind = c.pop("type", "CrossEntropyLoss")
+        if kind == "LovaszLoss":
+            extra = set(c) - {"mode", "class_seen", "per_image", "ignore_index", "loss_weight"}
+            if "mode" not in c or extra:
+                raise NotImplementedError("criteria LovaszLoss with %s%s: LovaszLoss(mode, class_seen, per_image, ignore_index, "
+                                          "loss_weight) is on the PT-v2m2 path" % (sorted(extra), "" if "mode" in c else
+                                                                                   ", without mode"))
+            loss = LovaszLoss(**c)
+            out.append((loss.loss_weight, loss.ignore_index, loss))
+            continue
         extra = set(c) - {"loss_weight", "ignore_index"}
         if kind != "CrossEntropyLoss" or extra:
-            raise NotImplementedError("criteria %r with %s: only CrossEntropyLoss(loss_weight, ignore_index) is on the "
-                                      "PT-v2m2 path" % (kind, sorted(extra)))
-        out.append((float(c.get("loss_weight", 1.0)), int(c.get("ignore_index", -1))))
+            raise NotImplementedError("criteria %r with %s: only CrossEntropyLoss(loss_weight, ignore_index) and "
+                                      "LovaszLoss(mode='multiclass', ...) are on the PT-v2m2 path" % (kind, sorted(extra)))
+        out.append((float(c.get("loss_weight", 1.0)), int(c.get("ignore_index", -1)), None))
     return out
 
 
 class DefaultSegmentor(nn.Module):
-    """backbone + CrossEntropyLoss(ignore_index=-1); constructor and return convention of the reference
+    """backbone + criteria (CrossEntropyLoss(ignore_index=-1) by default, LovaszLoss entries allowed); constructor and return convention of the reference
     (pointcept/models/default.py:232-251): `DefaultSegmentor(backbone=dict(type="PT-v2m2", ...), criteria=[dict(
     type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1)])`."""
 
@@ -114,14 +127,17 @@ class DefaultSegmentor(nn.Module):
         self.backbone = backbone if isinstance(backbone, nn.Module) else PointTransformerV2(
             **{k: v for k, v in dict(backbone).items() if k != "type"})
         self._criteria = _parse_criteria(criteria, ignore_index)
-        self.ignore_index = self._criteria[0][1]
+        self.ignore_index = next((i for _, i, lov in self._criteria if lov is None), ignore_index)
         self.criteria = nn.CrossEntropyLoss(ignore_index=self.ignore_index)  # kept for state / introspection parity
 
     def loss(self, seg_logits, segment):
         total = None
-        for weight, ignore in self._criteria:
-            term = cross_entropy(seg_logits, segment, ignore)
-            term = term if weight == 1.0 else term * weight
+        for weight, ignore, lovasz in self._criteria:
+            if lovasz is not None:  # (loss_weight applied inside, as the reference's LovaszLoss.forward)
+                term = lovasz(seg_logits, segment)
+            else:
+                term = cross_entropy(seg_logits, segment, ignore)
+                term = term if weight == 1.0 else term * weight
             total = term if total is None else total + term
         return total
 

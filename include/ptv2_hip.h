@@ -753,6 +753,24 @@ int cross_entropy_backward_hip_launcher(int n, int c, const float *logits, const
                                         const float *lse, const float *g_loss, const float *count, float *g_logits,
                                         void *stream);
 
+/* --------------------------------------------------- Lovasz-softmax loss --
+ * LovaszLoss(mode="multiclass", per_image=False) of pointcept/models/losses/lovasz.py:211-253 (ao_amd/csrc/lovasz.hip):
+ * weight * mean over the present classes (ascending; limited to class_seen when given) of the Lovasz extension of the
+ * class's Jaccard loss on the errors |fg - softmax(logits)[:, class]|, sorted descending with ties in ascending row order.
+ * logits (n,c) fp32, label (n) int64, 2 <= c <= 1024, n < 2^24.  Rows used: label != ignore_index, every row when
+ * has_ignore == 0.  class_seen: device int32 mask (c), nonzero = the class may be averaged; NULL = every class.
+ * out: 4 device floats (loss, classes averaged, bad labels, rows used); a label that is neither ignore_index nor in [0,c)
+ * is not used and makes the loss nan; no class to average -> loss 0 and a zero gradient.  saved (saved_bytes) is written
+ * by the forward and read by the backward of the same call; workspace is scratch of the forward alone.  The backward
+ * writes g_logits = p * (gp - <gp, p>) * g_loss * weight / classes, gp = dL/dp with the sort order held constant. */
+size_t lovasz_softmax_workspace_bytes(int n, int c);
+size_t lovasz_softmax_saved_bytes(int n, int c);
+int lovasz_softmax_forward_hip_launcher(int n, int c, const float *logits, const long long *label, int ignore_index,
+                                        int has_ignore, const int *class_seen, float weight, float *out, void *saved,
+                                        size_t saved_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int lovasz_softmax_backward_hip_launcher(int n, int c, const float *logits, const void *saved, float weight,
+                                         const float *g_loss, float *g_logits, void *stream);
+
 /* ------------------------------------------------- REAL's logit basket (host memory) --
  * dst (dst_rows, c) fp32 HOST array of one whole scene; dst[ids[r], :] = src[r, :] for r = 0 .. rows-1 in that order:
  * the trainer statement `self.basket[k][ori_idx] = seg` (pointcept/engines/train_sam_real.py:234).  ids int64, src
