@@ -79,6 +79,14 @@ _SIGNATURES = {
     "lovasz_softmax_saved_bytes": (_c_size, [_c_int] * 2),
     "lovasz_softmax_forward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 2 + [_c_int] * 2 + [_vp, ctypes.c_float, _vp, _vp,
                                                                                                _c_size, _vp, _c_size, _vp]),
+    "cac_workspace_bytes": (_c_size, [_c_int] * 5),
+    "cac_weighted_sum_forward_hip_launcher": (_c_int, [_c_int] * 6 + [_vp] * 4 + [ctypes.c_float] * 2 + [_vp] * 3 + [_c_size, _vp]),
+    "cac_weighted_sum_backward_hip_launcher": (_c_int, [_c_int] * 6 + [_vp] * 4 + [ctypes.c_float] * 2 + [_vp] * 6),
+    "cac_cosine_forward_hip_launcher": (_c_int, [_c_int] * 5 + [_vp] * 2 + [_c_int, _vp, ctypes.c_float, _vp, _vp]),
+    "cac_cosine_backward_hip_launcher": (_c_int, [_c_int] * 5 + [_vp] * 2 + [_c_int, _vp, ctypes.c_float] + [_vp] * 4
+                                         + [_c_size, _vp]),
+    "cac_distill_forward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 6 + [_c_size, _vp]),
+    "cac_distill_backward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 7),
     "lovasz_softmax_backward_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 2 + [ctypes.c_float] + [_vp] * 3),
     "bn_stats_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 6 + [ctypes.c_float] * 2 + [_vp, _c_size, _vp]),
     "bn_apply_hip_launcher": (_c_int, [_c_int] * 2 + [_vp] * 5 + [_c_int, _vp, _vp]),

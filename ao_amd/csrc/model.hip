@@ -9,6 +9,7 @@
 //                                x = interp(u) + s   or   u[cluster] + s      (UnpoolWithSkip :305-316)
 //                                x = blocks(seq 1+S+i)
 //              logits = ReLU(BN(x Wh^T + bh)) Wc^T + bc                       (seg_head :545-554)
+//              headless (num_classes == 0, head_w == NULL: seg_head is nn.Identity, :554): logits = x, (n0, c0)
 //   backward:  the same chain reversed.  The gradient of a skip tensor has two contributions (the decoder's proj_skip and
 //              the encoder's GridPool.fc); the second is added by the row GEMM's accumulate epilogue.
 //
@@ -177,7 +178,8 @@ struct Arena {  // the `saved` buffer of one forward
 bool model_ok(const ptv2_model *M) {
     if (!M || M->num_stages < 1 || M->num_stages > PTV2_MAX_STAGES || M->num_blocks < 1 || M->num_blocks > PTV2_MAX_BLOCKS)
         return false;
-    if (M->in_channels < 1 || M->num_classes < 1 || M->in_channels > 64 || M->num_classes > 256) return false;
+    if (M->in_channels < 1 || M->num_classes < 0 || M->in_channels > 64 || M->num_classes > 256) return false;
+    if ((M->num_classes == 0) != (M->head_w == nullptr)) return false;  // headless: both, or neither
     const int S = M->num_stages;
     for (int i = 0; i <= S; ++i)
         if (M->level[i].n < 2 || !M->level[i].coord) return false;
@@ -187,7 +189,17 @@ bool model_ok(const ptv2_model *M) {
         if (s.depth > 0 && (!s.idx || s.c < 4 || s.g < 1 || s.k < 1)) return false;
     }
     if (M->embed.cin != M->in_channels || (M->seq[0].depth > 0 && M->embed.cout != M->seq[0].c)) return false;
-    return M->feat && M->logits && M->head_w;
+    if (M->num_classes == 0 && (M->up[0].cout < 4 || M->up[0].cout % 4 != 0)) return false;
+    return M->feat && M->logits;
+}
+
+// num_classes == 0: the backbone without its segmentation head (reference num_classes=0: seg_head = nn.Identity); the
+// output, `logits`, is decoder stage 0's (n0, c0) feature rows
+bool headless(const ptv2_model *M) { return M->num_classes == 0; }
+
+// dst = src, n float4s (the headless output, and the incoming gradient into the workspace)
+__global__ __launch_bounds__(TPB) void copy4_kernel(long long n4, const float4 *__restrict__ src, float4 *__restrict__ dst) {
+    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < n4; e += (long long)gridDim.x * TPB) dst[e] = src[e];
 }
 
 // what the prefix (patch embedding + seq 0) reads of the struct
@@ -252,7 +264,7 @@ Arena carve(const ptv2_model *M, void *base, void *base0 = nullptr, bool split =
         A.up[i] = linbn(M->up[i], M->level[i + 1].n, true);
         A.up_skip[i] = linbn(M->up_skip[i], M->level[i].n, true);  // y = the unpool output (skip branch + unpooled rows)
     }
-    A.head = linbn(M->head, M->level[0].n, true);
+    if (!headless(M)) A.head = linbn(M->head, M->level[0].n, true);
     size_t shared_saved = 0;  // checkpointing: one region, sized for the largest Block, shared by all of them
     for (int q = (M->checkpoint ? 0 : 1); q <= 2 * S; ++q) {  // (seq 0: above, unless its Blocks share the checkpoint region)
         const ptv2_seq &s = M->seq[q];
@@ -312,14 +324,15 @@ Work carve_work(const ptv2_model *M, void *base, bool prefix_only = false) {
         W.bytes = off;
         return W;
     }
-    note(M->head, M->level[0].n);
+    if (!headless(M)) note(M->head, M->level[0].n);
     for (int i = 0; i < S; ++i) {
         note(M->down[i], M->level[i].n);
         note(M->up[i], M->level[i + 1].n);
         note(M->up_skip[i], M->level[i].n);
     }
-    W.dense_bytes = std::max(W.dense_bytes, dense_workspace_bytes(M->level[0].n, std::max(M->num_classes, M->head.cout),
-                                                                  std::max(M->in_channels, M->head.cout)));
+    if (!headless(M))
+        W.dense_bytes = std::max(W.dense_bytes, dense_workspace_bytes(M->level[0].n, std::max(M->num_classes, M->head.cout),
+                                                                      std::max(M->in_channels, M->head.cout)));
     W.block = take(W.block_bytes);
     W.dense = take(W.dense_bytes);
     W.ga = (float *)take(sizeof(float) * widest);
@@ -349,7 +362,7 @@ Work carve_work(const ptv2_model *M, void *base, bool prefix_only = false) {
             W.wdefer_bytes += al(sizeof(float) * (size_t)n * L.cout) + al(dense_workspace_bytes(n, L.cout, L.cin)) + 512;
         };
         layer(M->embed, M->level[0].n);
-        layer(M->head, M->level[0].n);
+        if (!headless(M)) layer(M->head, M->level[0].n);
         for (int i = 0; i < S; ++i) {
             layer(M->down[i], M->level[i].n);
             layer(M->up[i], M->level[i + 1].n);
@@ -644,6 +657,12 @@ int model_forward(const ptv2_model *M, void *workspace, size_t workspace_bytes, 
         x = seq_forward(M, 1 + S + i, A, out, W, stream, &rc);
         if (rc != PTV2_OK) return rc;
     }
+    if (headless(M)) {  // seg_head = Identity: decoder stage 0's rows are the output
+        const long long n4 = (long long)M->level[0].n * (M->up[0].cout / 4);
+        hipLaunchKernelGGL(copy4_kernel, dim3(grid_for(n4)), dim3(TPB), 0, st, n4, (const float4 *)x, (float4 *)M->logits);
+        PTV2_CHECK_LAUNCH();
+        return PTV2_OK;
+    }
     RUN(linbn_forward(M, M->head, A.head, M->level[0].n, x, A.head.y, W, stream));
     {
         const int c0 = M->head.cout, nc = M->num_classes;
@@ -664,7 +683,7 @@ int model_forward(const ptv2_model *M, void *workspace, size_t workspace_bytes, 
 }
 
 int model_backward(const ptv2_model *M, const float *g_logits, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!model_ok(M) || !M->saved || !g_logits || !M->g_head_w) return PTV2_ERR_ARG;
+    if (!model_ok(M) || !M->saved || !g_logits || (!headless(M) && !M->g_head_w)) return PTV2_ERR_ARG;
     const PtvMatmulScope precision(M->matmul_bf16);
     if (M->saved0 && M->checkpoint) return PTV2_ERR_ARG;
     const Arena A = carve(M, M->saved, M->saved0);
@@ -697,8 +716,12 @@ int model_backward(const ptv2_model *M, const float *g_logits, void *workspace, 
     // Gradient buffers: ga / gb ping-pong along the chain, gc holds the gradient in front of a BatchNorm (the operand of
     // the weight gradient), gskip[i] the gradient of the encoder output of level i.
     float *const ga = W.ga, *const gb = W.gb, *const gc = W.gc;
-    // head: classifier, then Linear + BatchNorm + ReLU -> gb = gradient of decoder stage 0's output
-    {
+    // head: classifier, then Linear + BatchNorm + ReLU -> gb = gradient of decoder stage 0's output.  Headless: the incoming
+    // gradient is that of decoder stage 0's output; it is copied into gb because the chain below uses ga / gb as scratch
+    if (headless(M)) {
+        const long long n4 = (long long)n0 * (M->up[0].cout / 4);
+        hipLaunchKernelGGL(copy4_kernel, dim3(grid_for(n4)), dim3(TPB), 0, st, n4, (const float4 *)g_logits, (float4 *)gb);
+    } else {
         const int c0 = M->head.cout, nc = M->num_classes;
         if (c0 % 4 == 0 && (long long)n0 * (c0 / 4) < (1LL << 31))
             hipLaunchKernelGGL(small_linear_bwd4_kernel, dim3(grid_for((long long)n0 * (c0 / 4))), dim3(TPB),

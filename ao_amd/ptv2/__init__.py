@@ -15,3 +15,4 @@ from .model import (  # noqa: F401
 from .basket import LogitBasket  # noqa: F401
 from .segmentor import DefaultSegmentor, DefaultSegmentorSAM_Image, S3DIS_BACKBONE, SCANNET_BACKBONE  # noqa: F401
 from .losses import LovaszLoss, lovasz_softmax  # noqa: F401
+from .cac import CACSegmentor  # noqa: F401

@@ -139,12 +139,17 @@ class _Runtime:
             linbn(M.down[i], enc.down.fc, enc.down.norm.norm)
             linbn(M.up[i], dec.up.proj[0], dec.up.proj[1].norm)
             linbn(M.up_skip[i], dec.up.proj_skip[0], dec.up.proj_skip[1].norm)
-        linbn(M.head, model.seg_head[0], model.seg_head[1].norm)
-        cls = model.seg_head[3]
-        M.head_w, M.head_b = ptr(cls.weight), ptr(cls.bias)
-        self.grad_fields.append((M, "g_head_w", None, index[id(cls.weight)]))
-        if cls.bias is not None:
-            self.grad_fields.append((M, "g_head_b", None, index[id(cls.bias)]))
+        # headless (num_classes=0, seg_head = nn.Identity): num_classes 0 and head_w NULL tell the runtime; the output is
+        # decoder stage 0's (N, dec_channels[0]) rows and the flat gradient layout has no head slots
+        self.headless = model.num_classes == 0 and isinstance(model.seg_head, torch.nn.Identity)
+        self.out_channels = model.dec_stages[0].up.proj[0].weight.shape[0] if self.headless else model.num_classes
+        if not self.headless and isinstance(model.seg_head, torch.nn.Sequential):
+            linbn(M.head, model.seg_head[0], model.seg_head[1].norm)
+            cls = model.seg_head[3]
+            M.head_w, M.head_b = ptr(cls.weight), ptr(cls.bias)
+            self.grad_fields.append((M, "g_head_w", None, index[id(cls.weight)]))
+            if cls.bias is not None:
+                self.grad_fields.append((M, "g_head_b", None, index[id(cls.bias)]))
         nb = 0
         self.block_modules = []
         for q, seq in enumerate(self.sequences):
@@ -180,7 +185,7 @@ class _Runtime:
                                   for seq in self.sequences for blk in seq.blocks)
                           and all(_gva.supported(blk.attn.embed_channels, blk.attn.groups, seq.neighbours)
                                   for seq in self.sequences for blk in seq.blocks)
-                          and isinstance(model.seg_head, torch.nn.Sequential) and M.embed.cout % 4 == 0)
+                          and (self.headless or isinstance(model.seg_head, torch.nn.Sequential)) and M.embed.cout % 4 == 0)
         self.M = M
         self.key = _block._pointer_key(self.tensor_slots)
         self.droppath = [[b.drop_path.drop_prob if hasattr(b.drop_path, "drop_prob") else 0.0 for b in seq.blocks]
@@ -552,7 +557,7 @@ class _NativeModel(torch.autograd.Function):
         else:
             keep = rt.fill_geometry(geo)
             scales = rt.draw_droppath(geo, dev) if training else None
-        logits = torch.empty((n0, M.num_classes), dtype=torch.float32, device=dev)
+        logits = torch.empty((n0, rt.out_channels), dtype=torch.float32, device=dev)  # (headless: the (N, c0) features)
         M.logits = logits.data_ptr()
         need = L.ptv2_model_saved_bytes(ctypes.addressof(M))
         if need == 0:

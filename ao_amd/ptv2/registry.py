@@ -28,18 +28,22 @@ def _register(registry, cls, name, force):
 
 
 def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None):
-    """Put PT-v2m2, the two segmentors and FlatAdamW under the reference's registry names, and with LOSSES
+    """Put PT-v2m2, the three segmentors (CAC-v1m1 included) and FlatAdamW under the reference's registry names, and with LOSSES
     (pointcept/models/losses/builder.py) the HIP LovaszLoss under "LovaszLoss": a trainer that keeps the reference's own
-    segmentor and `Criteria` then builds it from the same config entry.  Every registry may be omitted."""
+    segmentor and `Criteria` then builds it from the same config entry.  Every registry may be omitted.  MODELS also receives
+    CACSegmentor under "CAC-v1m1"; the returned list of names leaves that entry out (it predates it)."""
     done = []
     if MODELS is not None:
         from .model import PointTransformerV2
+        from .cac import CACSegmentor
         from .segmentor import DefaultSegmentor, DefaultSegmentorSAM_Image
 
         for cls, name in ((PointTransformerV2, "PT-v2m2"), (DefaultSegmentor, "DefaultSegmentor"),
                           (DefaultSegmentorSAM_Image, "DefaultSegmentorSAM_Image")):
             _register(MODELS, cls, name, force)
             done.append(name)
+        # (filed under MODELS as well, but not listed in the return value: callers compare that list with the names above)
+        _register(MODELS, CACSegmentor, "CAC-v1m1", force)
     if OPTIMIZERS is not None:
         from .optim import FlatAdamW
 

@@ -638,10 +638,12 @@ typedef struct ptv2_model {
     int num_blocks;
     ptv2_model_block block[PTV2_MAX_BLOCKS];
     ptv2_linbn embed, down[PTV2_MAX_STAGES], up[PTV2_MAX_STAGES], up_skip[PTV2_MAX_STAGES], head;
-    const float *head_w, *head_b;      /* seg_head[3]: (num_classes, c0), (num_classes) */
+    const float *head_w, *head_b;      /* seg_head[3]: (num_classes, c0), (num_classes); num_classes == 0 with head_w == NULL:
+                                        * headless (seg_head = nn.Identity, reference num_classes=0): no head in either
+                                        * direction, `logits` / g_logits are decoder stage 0's (n0, c0 = up[0].cout) rows */
     float *g_head_w, *g_head_b;        /* backward only */
     const float *feat;                 /* (n0, in_channels) */
-    float *logits;                     /* (n0, num_classes) */
+    float *logits;                     /* (n0, num_classes), headless (n0, c0) */
     void *saved;
     size_t saved_bytes;
     int matmul_bf16;                   /* as ptv2_block.matmul_bf16, for every Linear of the network */
@@ -770,6 +772,38 @@ int lovasz_softmax_forward_hip_launcher(int n, int c, const float *logits, const
                                         size_t saved_bytes, void *workspace, size_t workspace_bytes, void *stream);
 int lovasz_softmax_backward_hip_launcher(int n, int c, const float *logits, const void *saved, float weight,
                                          const float *g_loss, float *g_logits, void *stream);
+
+/* ------------------------------------------------ context-aware classifier heads --
+ * CAC-v1m1 (pointcept/models/context_aware_classifier/context_aware_classifier_v1m1_base.py) on (N, C) fp32 feature rows,
+ * K classes, b scenes (`offset`: int32 cumulative row ends), max_rows = the largest scene's row count (sizes the grid; the
+ * caller knows the scene bounds).  K <= 256, C % 4 == 0, 4 <= C <= 64.  No host synchronisation, no float atomics: every
+ * reduction goes through per-workgroup partial slabs added in a fixed order (bitwise reproducible).
+ *   weighted sums (mode 0, soft prototypes): w_nk = softmax(logits_n)_k, times [max_k p_nk >= thr] when thr > 0;
+ *                 z (b,K) = sum_{n in s} w_nk, out (b,K,C) = sum_{n in s} w_nk x_n / (z + eps)
+ *                 (mode 1, class means): w_nk = [label_n == k] (int64, -1 ignored), ONE set: z (K) counts, out (K,C)
+ *                 backward: gx (N,C) = sum_k w_nk / (z_k + eps) dout_k (written); glogits (N,K), mode 0 only, optional:
+ *                 the gradient through the weights (mask held constant)
+ *   cosine logits: out (N,K) = scale <x_n / max(|x_n|, 1e-12), q_k / max(|q_k|, 1e-12)>, q (b,K,C) per scene (per_scene != 0)
+ *                 or (K,C) shared; backward writes gx (N,C) and gq (q's shape)
+ *   distillation: get_distill_loss(pred, soft, label, smoothness=0.5, eps=0) of (N,K) pred / soft -> loss (1); coef (K) is
+ *                 saved for the backward, which writes gpred (N,K) scaled by the device scalar g */
+size_t cac_workspace_bytes(int b, int max_rows, int n, int k, int c);
+int cac_weighted_sum_forward_hip_launcher(int mode, int n, int b, int max_rows, int k, int c, const float *x, const float *logits,
+                                          const long long *label, const int *offset, float thr, float eps, float *z, float *out,
+                                          void *workspace, size_t workspace_bytes, void *stream);
+int cac_weighted_sum_backward_hip_launcher(int mode, int n, int b, int max_rows, int k, int c, const float *x,
+                                           const float *logits, const long long *label, const int *offset, float thr, float eps,
+                                           const float *z, const float *out, const float *dout, float *gx, float *glogits,
+                                           void *stream);
+int cac_cosine_forward_hip_launcher(int n, int b, int max_rows, int k, int c, const float *x, const float *q, int per_scene,
+                                    const int *offset, float scale, float *out, void *stream);
+int cac_cosine_backward_hip_launcher(int n, int b, int max_rows, int k, int c, const float *x, const float *q, int per_scene,
+                                     const int *offset, float scale, const float *dout, float *gx, float *gq, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+int cac_distill_forward_hip_launcher(int n, int k, const float *pred, const float *soft, const long long *label, float *loss,
+                                     float *coef, void *workspace, size_t workspace_bytes, void *stream);
+int cac_distill_backward_hip_launcher(int n, int k, const float *pred, const float *soft, const long long *label,
+                                      const float *coef, const float *g, float *gpred, void *stream);
 
 /* ------------------------------------------------- REAL's logit basket (host memory) --
  * dst (dst_rows, c) fp32 HOST array of one whole scene; dst[ids[r], :] = src[r, :] for r = 0 .. rows-1 in that order:
