@@ -2136,6 +2136,16 @@ int gva_wp2_wgrad_recompute(int n, int k, int c, int g, const float *g_out, cons
     return PTV2_OK;
 }
 
+// the public form of the above (include/ptv2_hip.h): the weight gradient that completes gva_attention_backward_hip_launcher,
+// launched at once with its own finalize (no backward is deferring on a thread that calls it from outside the model runtime)
+extern "C" int gva_attention_wgrad_hip_launcher(int n, int k, int c, int g, const float *g_out, const float *w, const float *sw,
+                                                const float *a, const float *b, const float *coord, const int *idx, float *dWp2,
+                                                float *dbp2, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!gva_wgrad_tile_supported(k, c, g) || n < 0) return PTV2_ERR_ARG;
+    if (n == 0) return PTV2_OK;
+    return gva_wp2_wgrad_recompute(n, k, c, g, g_out, w, sw, a, b, coord, idx, dWp2, dbp2, workspace, workspace_bytes, stream);
+}
+
 // internal (gva_block.hip): rowscale != NULL asks for db[b][o] = sum_n gY[n, b, o] * rowscale[n * lds_s + b] instead of the plain
 // column sums.  Only the LDS-staged fp32 kernel forms them: *weighted says whether it did (1) or whether the caller has to
 // compute db itself (0: db is then not written at all).

@@ -56,6 +56,7 @@ _SIG = {
     "gva_peb_backward_hip_launcher": (_lib._c_int, [_lib._c_int] * 3 + [_lib._vp] * 6),
     "gva_attention_forward_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 17),
     "gva_attention_backward_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 25 + [_lib._c_size, _lib._vp]),
+    "gva_attention_wgrad_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 10 + [_lib._c_size, _lib._vp]),
 }
 _lib.register(_SIG)
 
@@ -654,13 +655,15 @@ def grouped_vector_attention(mod, query, key, value, coord, reference_index, imp
     N, K = idx.shape
     rows = N * K
     coord = coord.contiguous()
-    query, key, value = query.float(), key.float(), value.float()
+    # (a float64 module stays float64: the torch restatement of the stages then serves as a high-precision reference)
+    f = (lambda t: t) if query.dtype == torch.float64 else (lambda t: t.float())
+    query, key, value = f(query), f(key), f(value)
     lin_p1, bn_p, lin_p2 = mod.linear_p_bias[0], mod.linear_p_bias[1].norm, mod.linear_p_bias[3]
     lin_w1, bn_w, lin_w2 = mod.weight_encoding[0], mod.weight_encoding[1].norm, mod.weight_encoding[3]
     training_stats = mod.training or not bn_p.track_running_stats or bn_p.running_mean is None
 
     # -- BN_p folded into an affine map of pos: P = ReLU(pos a^T + b) -----------------------------
-    Wp1, bp1 = lin_p1.weight.float(), lin_p1.bias.float()
+    Wp1, bp1 = f(lin_p1.weight), f(lin_p1.bias)
     mu = cov = None
     if training_stats:
         mu, cov = _pos_moments(impl, coord, idx)
@@ -668,20 +671,20 @@ def grouped_vector_attention(mod, query, key, value, coord, reference_index, imp
         a, b = impl.fold_p(lin_p1, bn_p, mu, cov, rows, training_stats)
     else:
         if training_stats:
-            mu32, cov32 = mu.float(), cov.float()
+            mu32, cov32 = f(mu), f(cov)
             mean_p = Wp1 @ mu32 + bp1
             var_p = ((Wp1 @ cov32) * Wp1).sum(1).clamp_min(0)
             if mod.training:
                 _bn_update(bn_p, mean_p, var_p, rows)
         else:
-            mean_p, var_p = bn_p.running_mean.float(), bn_p.running_var.float()
-        scale_p = bn_p.weight.float() * torch.rsqrt(var_p + bn_p.eps)
+            mean_p, var_p = f(bn_p.running_mean), f(bn_p.running_var)
+        scale_p = f(bn_p.weight) * torch.rsqrt(var_p + bn_p.eps)
         a = Wp1 * scale_p.unsqueeze(1)
-        b = (bp1 - mean_p) * scale_p + bn_p.bias.float()
+        b = (bp1 - mean_p) * scale_p + f(bn_p.bias)
 
     # -- logits: W1 = kW[idx] - qW + P M + cW ------------------------------------------------------
-    Wp2, bp2 = lin_p2.weight.float(), lin_p2.bias.float()
-    Ww1, bw1 = lin_w1.weight.float(), lin_w1.bias.float()
+    Wp2, bp2 = f(lin_p2.weight), f(lin_p2.bias)
+    Ww1, bw1 = f(lin_w1.weight), f(lin_w1.bias)
     M = Wp2.t() @ Ww1.t()                      # (C,G): M[c',g] = sum_c Wp2[c,c'] Ww1[g,c]
     cW = torch.addmv(bw1, Ww1, bp2)
     kW = skinny_linear(key, Ww1)
@@ -702,10 +705,10 @@ def grouped_vector_attention(mod, query, key, value, coord, reference_index, imp
             mean_w, var_w = bn_w.running_mean.double(), bn_w.running_var.double()
         sc64 = bn_w.weight.double() * torch.rsqrt(var_w + bn_w.eps)
         sh64 = bn_w.bias.double() - mean_w * sc64
-        sc, sh = sc64.float(), sh64.float()
+        sc, sh = f(sc64), f(sh64)
 
     # -- softmax over neighbours, aggregation of v and of the folded positional bias ---------------
-    out_v, A, sw = impl.aggregate(W1, sc, sh, lin_w2.weight.float(), lin_w2.bias.float(), value, a, b, coord, idx)
+    out_v, A, sw = impl.aggregate(W1, sc, sh, f(lin_w2.weight), f(lin_w2.bias), value, a, b, coord, idx)
     if hasattr(impl, "project"):
         return impl.project(A, Wp2, bp2, sw, out_v)
     peb = torch.einsum("ngc,gic->ngi", A, Wp2.view(G, I, C))

@@ -303,7 +303,8 @@ int gva_attention_forward_hip_launcher(int n, int k, int c, int g, const float *
  * shapes): given w (n,k,g) of the forward and g_out (n,c) -- g_A = g_out Wp2 per group is formed in LDS per 16-channel chunk,
  * never in memory -- writes gW1 (n,k,g), gsc, gsh (g), gWw2 (g,g), gbw2 (g), gv (n,c), ga (c,3), gb (c) (the gradients of the
  * folded positional encoding P = ReLU(a . pos + b)).  inv_ptr / inv_rows: the inverse neighbour table (inverse_table);
- * workspace: gva_aggregate_workspace_bytes(n,k,c,g).  grad Wp2 / bp2 (direct parts) are the caller's (a weight gradient). */
+ * workspace: gva_aggregate_workspace_bytes(n,k,c,g).  grad Wp2 / bp2 (direct parts) are a weight gradient of their own:
+ * gva_attention_wgrad_hip_launcher below. */
 int gva_attention_backward_hip_launcher(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
                                         const float *Ww2, const float *bw2, const float *v, const float *a,
                                         const float *b, const float *coord, const int *idx, const float *w,
@@ -311,6 +312,14 @@ int gva_attention_backward_hip_launcher(int n, int k, int c, int g, const float 
                                         const int *inv_rows, float *gW1, float *gsc, float *gsh, float *gWw2, float *gbw2,
                                         float *gv, float *ga, float *gb, void *workspace, size_t workspace_bytes,
                                         void *stream);
+/* The weight gradient that completes the pair (ao_amd/csrc/gva_wgrad_tile.hip; the same shapes, PTV2_ERR_ARG otherwise; n = 0
+ * does nothing): dWp2 (c,c) [8 g + i, c'] = sum_n g_out[n, 8 g + i] A[n, g, c'] with A = w^T P formed again from the forward's
+ * w (n,k,g) -- no (n,g,c) tensor is read --, and dbp2 (c) = sum_n g_out[n, 8 g + i] sw[n, g] (the direct part of grad bp2).
+ * Split over the points into at most n / 128 + 1 partial records that a finalize sums in a fixed order.
+ * workspace: dense_workspace_bytes(n, c, c). */
+int gva_attention_wgrad_hip_launcher(int n, int k, int c, int g, const float *g_out, const float *w, const float *sw,
+                                     const float *a, const float *b, const float *coord, const int *idx, float *dWp2,
+                                     float *dbp2, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------ whole attention block, one call --
  * GroupedVectorAttention.forward / backward (point_transformer_v2m2_base.py:103-129) behind ONE launcher each:
