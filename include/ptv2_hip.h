@@ -422,7 +422,9 @@ int segment_sum_hip_launcher(int n_out, int c, const float *grad_fine, const int
  * PointBatchNorm on (N,C) rows (point_transformer_v2m2_base.py:26-45: nn.BatchNorm1d) with an optional
  * fused ReLU, and the weight/bias gradient of nn.Linear as a split-K reduction.  c % 4 == 0, c <= 1024.
  *   bn_stats:    batch mean / rstd (biased variance) of x (n,c); when running_mean != NULL also the
- *                momentum update of running_mean / running_var (unbiased) and ++*num_batches_tracked
+ *                momentum update of running_mean / running_var (unbiased) and ++*num_batches_tracked.
+ *                n = 1 is accepted (nn.BatchNorm1d raises in training mode): mean = x, rstd = eps^-1/2, and
+ *                running_var, whose unbiased estimate is 0 / 0, takes the biased variance, 0
  *   bn_apply:    y = (x - mean) * rstd * gamma + beta, then max(.,0) if relu
  *   bn_backward: gx, dgamma, dbeta from gy (n,c); relu != 0 masks gy where the forward output was <= 0;
  *                training == 0 treats mean / rstd as constants (eval mode)
