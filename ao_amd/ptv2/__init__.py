@@ -16,3 +16,4 @@ from .basket import LogitBasket  # noqa: F401
 from .segmentor import DefaultSegmentor, DefaultSegmentorSAM_Image, S3DIS_BACKBONE, SCANNET_BACKBONE  # noqa: F401
 from .losses import LovaszLoss, lovasz_softmax  # noqa: F401
 from .cac import CACSegmentor  # noqa: F401
+from .tester import SemSegTester, VoteTable, test_scene  # noqa: F401

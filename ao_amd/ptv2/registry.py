@@ -27,10 +27,12 @@ def _register(registry, cls, name, force):
         registry.register_module(module=cls, name=name)
 
 
-def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None):
+def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
     """Put PT-v2m2, the three segmentors (CAC-v1m1 included) and FlatAdamW under the reference's registry names, and with LOSSES
     (pointcept/models/losses/builder.py) the HIP LovaszLoss under "LovaszLoss": a trainer that keeps the reference's own
-    segmentor and `Criteria` then builds it from the same config entry.  Every registry may be omitted.  MODELS also receives
+    segmentor and `Criteria` then builds it from the same config entry; with TEST (pointcept/engines/test.py:26) the whole-scene
+    tester of ao_amd/ptv2/tester.py under "SemSegTester", which `test = dict(type="SemSegTester")` then resolves to.  Every
+    registry may be omitted.  MODELS also receives
     CACSegmentor under "CAC-v1m1"; the returned list of names leaves that entry out (it predates it)."""
     done = []
     if MODELS is not None:
@@ -54,4 +56,9 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None):
 
         _register(LOSSES, LovaszLoss, "LovaszLoss", force)
         done.append("LovaszLoss")
+    if TEST is not None:
+        from .tester import SemSegTester
+
+        _register(TEST, SemSegTester, "SemSegTester", force)
+        done.append("SemSegTester")
     return done

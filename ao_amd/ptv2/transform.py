@@ -6,10 +6,23 @@ Same constructor arguments, dictionary keys and results as pointcept/datasets/tr
 the reference runs these in numpy on 16 CPU workers per GPU; here a raw scan is voxelised and cropped on the GPU
 that trains on it (voxel keys / squared distances: ao_amd/csrc/dataops.hip; sort / run-length: torch = rocPRIM).
 
+The test-time pipeline (pointcept/datasets/s3dis.py:212-236) is here too: the transforms the PT-v2m2 test configs name
+(CenterShift :129-142, NormalizeColor :100-104, RandomScale :285-296, RandomFlip :300-315, RandomRotateTargetAngle :246-281,
+ToTensor, Compose :1107-1117) and `test_fragments`, which builds the reference's `fragment_list` from them.  These are plain
+torch on whatever device the data is on.  Arithmetic: the reference works on fp32 numpy arrays and multiplies / rotates with
+float64 operands, so `coord *= scale` is one float64 product rounded to fp32 -- done the same way here (bitwise equal).  Its
+rotation `np.dot(coord, rot_t.T)` turns `coord` into a float64 array that stays float64 until ToTensor; here the rotation
+(and the centre shift around it) is computed in float64 with the same matrix and rounded to fp32 ONCE, right after it, so
+that GridSample sees fp32 as everywhere else in this module: the coordinates equal the reference's final fp32 values to
+1 ulp, and a point within that distance of a voxel border can land in the neighbouring voxel.
+
 Where the reference's result depends on numpy's unstable argsort (which point of a voxel a given draw selects, the
 order of equidistant points) the order here is the stable one -- ascending original index among equals.  Random
 choices come from a torch.Generator (or are passed in), not from numpy's global RNG.
 """
+import copy
+import math
+
 import torch
 
 from .. import _lib
@@ -204,6 +217,173 @@ class Collect:
         for name, keys in self.kwargs.items():
             data[name.replace("_keys", "")] = torch.cat([data_dict[key].float() for key in keys], dim=1)
         return data
+
+
+class CenterShift:
+    def __init__(self, apply_z=True):
+        self.apply_z = apply_z
+
+    def __call__(self, data_dict):
+        if "coord" in data_dict.keys():
+            coord = data_dict["coord"]
+            lo, hi = coord.min(dim=0)[0], coord.max(dim=0)[0]
+            shift = torch.stack([(lo[0] + hi[0]) / 2, (lo[1] + hi[1]) / 2, lo[2] if self.apply_z else torch.zeros_like(lo[2])])
+            data_dict["coord"] = coord - shift
+        return data_dict
+
+
+class NormalizeColor:
+    def __call__(self, data_dict):
+        if "color" in data_dict.keys():
+            color = data_dict["color"]
+            # (a tensor divisor: with a python scalar torch multiplies by the rounded reciprocal on the GPU, 1 ulp off
+            # numpy's IEEE division)
+            data_dict["color"] = color / torch.full((1,), 127.5, dtype=color.dtype, device=color.device) - 1
+        return data_dict
+
+
+def _uniform(lo, hi, size, generator):
+    """np.random.uniform(lo, hi, size) from a torch.Generator: float64 on the host; lo == hi gives lo exactly"""
+    return float(lo) + (float(hi) - float(lo)) * torch.rand(size, dtype=torch.float64, generator=generator)
+
+
+class RandomScale:
+    def __init__(self, scale=None, anisotropic=False):
+        self.scale = scale if scale is not None else [0.95, 1.05]
+        self.anisotropic = anisotropic
+
+    def __call__(self, data_dict, generator=None, scale=None):
+        if "coord" in data_dict.keys():
+            if scale is None:
+                scale = _uniform(self.scale[0], self.scale[1], 3 if self.anisotropic else 1, generator)
+            coord = data_dict["coord"]
+            scale = torch.as_tensor(scale, dtype=torch.float64).to(coord.device)
+            data_dict["coord"] = (coord.double() * scale).to(coord.dtype)  # a float64 product rounded once, as numpy's *=
+        return data_dict
+
+
+class RandomFlip:
+    def __init__(self, p=0.5):
+        self.p = p
+
+    def __call__(self, data_dict, generator=None, draws=None):
+        if draws is None:
+            draws = torch.rand(2, dtype=torch.float64, generator=generator).tolist()
+        for axis, u in enumerate(draws):
+            if u < self.p:
+                for key in ("coord", "normal"):
+                    if key in data_dict.keys():
+                        v = data_dict[key].clone()
+                        v[:, axis] = -v[:, axis]
+                        data_dict[key] = v
+        return data_dict
+
+
+class RandomRotateTargetAngle:
+    def __init__(self, angle=(1 / 2, 1, 3 / 2), center=None, axis="z", always_apply=False, p=0.75):
+        self.angle, self.axis, self.always_apply, self.center = angle, axis, always_apply, center
+        self.p = p if not always_apply else 1
+
+    def matrix(self, angle):
+        """rot_t of transform.py:260-266 for `angle` (in units of pi), float64"""
+        a = angle * math.pi
+        c, s = math.cos(a), math.sin(a)
+        if self.axis == "x":
+            rows = [[1, 0, 0], [0, c, -s], [0, s, c]]
+        elif self.axis == "y":
+            rows = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
+        elif self.axis == "z":
+            rows = [[c, -s, 0], [s, c, 0], [0, 0, 1]]
+        else:
+            raise NotImplementedError
+        return torch.tensor(rows, dtype=torch.float64)
+
+    def __call__(self, data_dict, generator=None, angle=None):
+        if float(torch.rand((), dtype=torch.float64, generator=generator)) > self.p:
+            return data_dict
+        if angle is None:
+            angle = self.angle[int(torch.randint(0, len(self.angle), (), generator=generator))]
+        if "coord" in data_dict.keys():
+            coord = data_dict["coord"]
+            rot = self.matrix(angle).to(coord.device)
+            if self.center is None:
+                centre = (coord.min(dim=0)[0] + coord.max(dim=0)[0]) / 2  # fp32, as the reference's scalars
+            else:
+                centre = torch.tensor([float(v) for v in self.center], dtype=torch.float64, device=coord.device)
+            moved = (coord.double() - centre.double()).to(coord.dtype)  # `coord -= center` rounds to fp32 in place
+            data_dict["coord"] = (moved.double() @ rot.t() + centre.double()).to(coord.dtype)
+        if "normal" in data_dict.keys():
+            normal = data_dict["normal"]
+            data_dict["normal"] = (normal.double() @ self.matrix(angle).to(normal.device).t()).to(normal.dtype)
+        return data_dict
+
+
+class ToTensor:
+    """The data is tensors already: a pass-through (numpy arrays, which the reference converts here, are converted too)."""
+
+    def __call__(self, data):
+        if torch.is_tensor(data) or isinstance(data, str):
+            return data
+        if isinstance(data, dict):
+            return {k: self(v) for k, v in data.items()}
+        if isinstance(data, (list, tuple)):
+            return [self(v) for v in data]
+        if isinstance(data, int):
+            return torch.tensor([data], dtype=torch.int64)
+        if isinstance(data, float):
+            return torch.tensor([data], dtype=torch.float32)
+        t = torch.as_tensor(data)
+        return t.float() if t.is_floating_point() else (t if t.dtype == torch.bool else t.long())
+
+
+def build_transform(cfg):
+    """`TRANSFORMS.build(cfg)` against this module's classes: dict(type="GridSample", ...) -> GridSample(...)."""
+    args = dict(cfg)
+    kind = args.pop("type")
+    cls = _TRANSFORMS.get(kind)
+    if cls is None:
+        raise KeyError("%s is not a transform of ao_amd.ptv2.transform (%s)" % (kind, sorted(_TRANSFORMS)))
+    return cls(**args)
+
+
+class Compose:
+    def __init__(self, cfg=None):
+        self.cfg = cfg if cfg is not None else []
+        self.transforms = [t if callable(t) else build_transform(t) for t in self.cfg]
+
+    def __call__(self, data_dict):
+        for t in self.transforms:
+            data_dict = t(data_dict)
+        return data_dict
+
+
+def test_fragments(data_dict, test_cfg, transform=None):
+    """S3DISDataset.prepare_test_data (datasets/s3dis.py:212-236) on device tensors: `dict(fragment_list, segment, name)`.
+    data_dict: coord (+ color, normal), segment, optional name; test_cfg: the config's own dict (voxelize, crop,
+    post_transform, aug_transform), its `type=` entries resolved against this module; transform: the dataset's base
+    transform as a list of configs or a callable."""
+    get = (lambda k: test_cfg.get(k)) if isinstance(test_cfg, dict) else (lambda k: getattr(test_cfg, k, None))
+    data_dict = dict(data_dict)
+    segment = data_dict.pop("segment")
+    name = data_dict.pop("name", "scene")
+    if transform is not None:
+        data_dict = (transform if callable(transform) else Compose(transform))(data_dict)
+    voxelize = build_transform(get("voxelize"))
+    crop = build_transform(get("crop")) if get("crop") else None
+    post = Compose(get("post_transform"))
+    fragment_list = []
+    for aug in get("aug_transform"):
+        data = Compose(aug)(copy.deepcopy(data_dict))
+        for part in voxelize(data):
+            fragment_list += crop(part) if crop is not None else [part]
+    return dict(fragment_list=[post(part) for part in fragment_list], segment=segment, name=name)
+
+
+test_fragments.__test__ = False  # (a library function, not a pytest case, whatever module imports it)
+
+_TRANSFORMS = dict(GridSample=GridSample, SphereCrop=SphereCrop, Collect=Collect, CenterShift=CenterShift,
+                   NormalizeColor=NormalizeColor, RandomScale=RandomScale, RandomFlip=RandomFlip,
+                   RandomRotateTargetAngle=RandomRotateTargetAngle, ToTensor=ToTensor)
 
 
 def point_collate(batch):

@@ -847,6 +847,19 @@ int center_dist2_hip_launcher(int n, const float *coord, const float *center, fl
 int seg_confusion_hip_launcher(long long n, int k, int ignore_index, const long long *pred, long long pred_n,
                                const int *nn_idx, const long long *target, long long *hist, void *stream);
 
+/* ------------------------------------------------ test-time voting (§8f) --
+ * Whole-scene inference (pointcept/engines/test.py:94-123), ao_amd/csrc/vote.hip.
+ * seg_vote_add: votes[index[i], :] += softmax(logits[i, :]) for ONE fragment: logits (n, c) fp32, or bf16 when logits_bf16;
+ * index (n) int32, or int64 when index_i64, without duplicates (a fragment holds a point at most once); votes (n_total, c)
+ * fp32; 2 <= c <= 1024.  Asynchronous.  status: one int32 of device memory, zero before the first call.  A segment with a
+ * row outside [0, n_total) sets it and writes nothing, and neither does any later call while it is set.
+ * seg_vote_status reads the word back (one host synchronisation): PTV2_OK, or PTV2_ERR_ARG after clearing it.
+ * seg_vote_argmax: pred (n_total) int64 = the first maximal class of every row (`votes.max(1)[1]`). */
+int seg_vote_add_hip_launcher(int n, int c, const void *logits, int logits_bf16, const void *index, int index_i64,
+                              float *votes, long long n_total, int *status, void *stream);
+int seg_vote_status_hip_launcher(int *status, void *stream);
+int seg_vote_argmax_hip_launcher(long long n_total, int c, const float *votes, long long *pred, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
