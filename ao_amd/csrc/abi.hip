@@ -63,7 +63,7 @@ void launch_alone(const PtvRider &r, hipStream_t st) {
 }
 }  // namespace
 bool ptv2_rider_defer_active() {
-    static const bool off = [] { const char *e = getenv("AO_AMD_RIDERS"); return e && e[0] == '0'; }();  // A/B switch (tests)
+    static const bool off = ptv2_env_is("AO_AMD_RIDERS", '0');  // A/B switch (tests)
     return g_defer_depth > 0 && !off;
 }
 void ptv2_rider_defer_depth(int delta) { g_defer_depth += delta; }

@@ -17,12 +17,6 @@
 
 #include "common.h"
 
-size_t bn_tiles_floats_rb(int n, int c, int rb);  // dense.hip: statistics records of rb rows each
-void ptv2_skinny_bn_arm(int n, int c, const float *const *x, const float *const *gy, const float *const *mean, const float *const *rstd,
-                        const float *const *gamma, const float *const *beta, int relu, void *workspace, size_t workspace_bytes);
-void ptv2_skinny_bn_disarm(void);
-int gva_block_keeps_A(int k, int c, int g);        // gva_block.hip
-
 namespace {
 
 inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -178,19 +172,6 @@ extern "C" int ptv2_block_param_layout(int c, int g, long long *offsets) {
 
 static bool use_batch(const ptv2_block *B, int i) { return B->training || !B->run_mean[i] || !B->run_var[i]; }
 
-// statistics of BatchNorm `i` (input h, (n,c)) -> S.mean / S.rstd / S.sc / S.sh: from the producing GEMM's epilogue
-// records (`part` != NULL), from a pass over h (`part` == NULL, batch statistics), or from the running buffers (eval)
-int bn_tiles_finalize_rb(int n, int c, int rb, float *part, const float *gamma, const float *beta, float *mean, float *rstd, float *sc,
-                         float *sh, float *running_mean, float *running_var, long long *num_batches_tracked, float eps, float momentum,
-                         void *stream);
-int bn_tiles_finalize_pair(int n, int c, float *const *part, const float *const *gamma, const float *const *beta,
-                           float *const *mean, float *const *rstd, float *const *sc, float *const *sh, float *const *running_mean,
-                           float *const *running_var, long long *const *num_batches_tracked, float eps, float momentum,
-                           void *stream, int rb);
-// gemm.hip: rows per statistics / reduce record the fused row GEMMs write for a shape (16: the deep levels' k-split kernel),
-// and the switch that tells them this caller reads either
-int rows_gemm_record_rows(int m, int n, int k);
-void ptv2_gemm_allow_rb16(int on);
 namespace {
 struct GemmRb16Scope {
     GemmRb16Scope() { ptv2_gemm_allow_rb16(1); }
@@ -198,6 +179,8 @@ struct GemmRb16Scope {
 };
 }  // namespace
 
+// statistics of BatchNorm `i` (input h, (n,c)) -> S.mean / S.rstd / S.sc / S.sh: from the producing GEMM's epilogue
+// records (`part` != NULL), from a pass over h (`part` == NULL, batch statistics), or from the running buffers (eval)
 static int bn_prepare(const ptv2_block *B, int i, const float *h, float *part, const float *gamma, const float *beta,
                       const Saved &S, const Work &W, void *stream, int rb = 64) {
     if (use_batch(B, i)) {
@@ -218,14 +201,6 @@ static int bn_prepare(const ptv2_block *B, int i, const float *h, float *part, c
                        S.bsc[i], S.bsh[i]);
     return PTV2_OK;
 }
-
-int gva_fold_forward_batched(int count, const ptv2_gva_block *blocks, void *stream);
-int bn_tiles_apply_residual(int n, int c, float *part, const float *gamma, const float *beta, float *mean, float *rstd, float *sc,
-                            float *sh, float *running_mean, float *running_var, long long *num_batches_tracked, float eps,
-                            float momentum, const float *x, const float *residual, const float *rowscale, float *y, void *stream,
-                            int rb);
-int gva_block_forward_stats(const ptv2_gva_block *B, float *out_stats, int *stats_done, void *workspace, size_t workspace_bytes,
-                            void *stream);
 
 // internal to the library (model.hip): the parameter-only folds of `count` Blocks in one launch per 8 Blocks, ahead of the
 // forward; the Blocks are then run inside ptv2_gva_set_prefolded(1)
@@ -338,7 +313,7 @@ extern "C" int ptv2_block_backward_hip_launcher(const ptv2_block *B, const ptv2_
     // as ONE launch + one finalize at the end of the block instead of three launches spread along the chain
     float *g_h3 = W.t[0], *g_hq = W.t[1], *g_hk = W.t[2], *gv = W.t[3], *g_h1 = W.t[4], *ta = W.t[5], *tb = W.t[6];
     // inside a model backward those five live in the deferral arena instead (the workspace is the next Block's too) and the
-    // launch at the end of this function is filed, to run with every other Block's at the end of the backward (dense.hip)
+    // launch at the end of this function is filed, to run with every other Block's at the end of the backward (wgrad.hip)
     // -- and so does g_attn, the gradient of the attention's output (norm2's backward writes it, the grouped projection's weight
     // gradient reads it; tb, its place otherwise, is reused for g_f1 further down)
     float *kept = ptv2_wgrad_defer_active() ? ptv2_wgrad_defer_alloc(6 * (size_t)n * c) : nullptr;
@@ -383,7 +358,7 @@ extern "C" int ptv2_block_backward_hip_launcher(const ptv2_block *B, const ptv2_
     VG.ggamma_w = GP(PTV2_BLK_WN_G); VG.gbeta_w = GP(PTV2_BLK_WN_B); VG.gWw2 = GP(PTV2_BLK_W2_W); VG.gbw2 = GP(PTV2_BLK_W2_B);
     if (!G->inv_ptr) (void)ptv2_zero_async(gv, sizeof(float) * (size_t)n * c, (hipStream_t)stream);
     // the attention backward's last launch (the skinny input gradients gk, gq) also leaves the reduce records of the two
-    // BatchNorm backwards that consume them (dense.hip skinny_bn_bwd_reduce_kernel): one launch fewer per Block
+    // BatchNorm backwards that consume them (skinny.hip skinny_bn_bwd_reduce_kernel): one launch fewer per Block
     if (batch[1] == batch[2]) {
         const float *xs[2] = {S.hk, S.hq}, *gys[2] = {gk, gq}, *ms[2] = {S.mean[2], S.mean[1]}, *rs[2] = {S.rstd[2], S.rstd[1]};
         const float *gs[2] = {P[PTV2_BLK_KN_G], P[PTV2_BLK_QN_G]}, *bs[2] = {P[PTV2_BLK_KN_B], P[PTV2_BLK_QN_B]};

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/ptv2_hip.h"
 
@@ -13,6 +14,33 @@
     } while (0)
 
 static inline int divup(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// The A/B switches of the library (environment variables; the parity tests flip them), all read through these two helpers.
+// A site that keeps the result in a `static const` reads once per process, any other site on every call -- part of the test
+// contract: the per-call ones are flipped with monkeypatch.setenv, tests/test_gpu_env_variants.py starts a child for the others.
+//   name                      unit                       read       meaning
+//   AO_AMD_BWD_STAGED         gva_aggregate.hip          per call   set: staged launches in every attention stage (gva_bwd_staged())
+//   AO_AMD_BWD_POINT          gva_aggregate.hip          per call   set: the point kernel instead of the backward tile kernel
+//   AO_AMD_FWD_STAGED         gva_block.hip              per call   set: the three staged forward launches (gva_fwd_staged())
+//   AO_AMD_TILE_KEEP_A        gva_block.hip              per call   set: the tile forward writes A (the A-reading weight gradient)
+//   AO_AMD_LOGITS_BWD         gva_bwd.hip                per call   "staged": the three-kernel logits backward (first letter s)
+//   AO_AMD_BN_FINAPPLY        bn.hip                     per call   0: separate finalize + apply launches (bn_finapply_off())
+//   AO_AMD_GEMM               gemm.hip                   per call   "direct" | "lds": the older row GEMM forms (plain getenv: first letter d / l)
+//   AO_AMD_FPS_LOCAL          fps.hip                    per call   0: the device-scope exchange instead of one XCD per cloud
+//   AO_AMD_GRAPH_IDLE_EAGER   graph.hip                  per call   0: launch the graph also when the stream is idle
+//   AO_AMD_GRAPH              graph.hip                  per process (first use; ptv2_graph_mode overrides)   0: no graph capture
+//   AO_AMD_WGRAD_DEFER        model.hip                  per process (first use; ptv2_wgrad_defer_mode overrides)   0: launch where called
+//   AO_AMD_GRAPH_LEAD         graph.hip                  per process   a number: graphs launched ahead (plain getenv + atoi)
+//   AO_AMD_GRAPH_DEBUG        graph.hip                  per process   1: print what each scope captured
+//   AO_AMD_GEMM_KSPLIT        gemm.hip                   per process   1: the k-split row GEMM at the deep levels
+//   AO_AMD_RIDERS             abi.hip                    per process   0: parameter-gradient sums run as launches of their own
+//   AO_AMD_BT_MIXED           gva_bwd_tile.hip           per process   0: one tile size per launch
+//   AO_AMD_SKINNY_BN          skinny.hip                 per process   0: the q / k BatchNorm reduce stays a launch of its own
+//   AO_AMD_WP2_GROUPED        wgrad.hip                  per process   0: the strided matrix-core form for the grouped projection
+//   AO_AMD_KNN_OCC            knn.hip                    per process   a number: occupancy target of the kNN grid (plain getenv + atof)
+static inline bool ptv2_env_set(const char *name) { return getenv(name) != nullptr; }  // the variable exists
+// ... and its first character is c
+static inline bool ptv2_env_is(const char *name, char c) { const char *e = getenv(name); return e && e[0] == c; }
 
 // Optional per-kernel timing for bench.py's roofline leg (abi.hip): when enabled through
 // ptv2_profile_enable(1), launchers bracket their main kernel with HIP events on the launch stream.
@@ -59,7 +87,7 @@ int ptv2_profile_stamps(void);    // the kernel timer brackets with device time 
 // zero-fill as a kernel launch (a kernel node like every other launch of a captured sequence; bytes % 4 == 0)
 int ptv2_zero_async(void *p, size_t bytes, hipStream_t st);
 
-// dense.hip: the weight-gradient launches of a model backward, filed where they are called and run by one launch at its end
+// wgrad.hip: the weight-gradient launches of a model backward, filed where they are called and run by one launch at its end
 void ptv2_wgrad_defer_begin(void *arena, size_t bytes);   // arena: job table + operands that must outlive their Block + records
 bool ptv2_wgrad_defer_active();
 float *ptv2_wgrad_defer_alloc(size_t floats);             // NULL: not deferring, or no room (the caller launches at once)
@@ -148,3 +176,5 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
     int q = nwg >> 3, r = nwg & 7, x = orig & 7;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (orig >> 3);
 }
+
+#include "internal.h"

@@ -109,7 +109,6 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float *__restric
     }
 }
 
-
 // ------------------------------------------------------------- cooperative FPS --
 // W workgroups per cloud (W <= 32), every point of the cloud resident in VGPRs (RC = 2, 4, 8 or 16 per lane), one exchange
 // per sample.  A workgroup publishes its best candidate as four 8-byte granules, stored as two 16-byte pairs:
@@ -406,9 +405,8 @@ extern "C" int farthest_point_sampling_hip_launcher(int b, int n_max, const floa
         unsigned long long *slots = (unsigned long long *)workspace;
         // one XCD per cloud (see the kernel): the launch carries enough workgroups that W - 1 of them may be left over on every
         // XCD, and all of it has to be resident at once; AO_AMD_FPS_LOCAL=0: the device-scope exchange (the tests' A/B switch)
-        const char *le = getenv("AO_AMD_FPS_LOCAL");
         const int local_grid = (b - 1) * W + 8 * (W - 1) + 1;
-        const bool local = !(le && le[0] == '0') && local_grid <= coop_capacity(RC) && (b + 7) / 8 + 1 <= COOP_TEAMS;
+        const bool local = !ptv2_env_is("AO_AMD_FPS_LOCAL", '0') && local_grid <= coop_capacity(RC) && (b + 7) / 8 + 1 <= COOP_TEAMS;
         int *err = (int *)((char *)workspace + sizeof(unsigned long long) * 2 * 4 * 256 * (size_t)b);
         int *ctrl = err + 16;
         (void)hipMemsetAsync(workspace, 0, sizeof(unsigned long long) * 2 * 4 * 256 * (size_t)b + sizeof(int) * (16 + COOP_CTRL_INTS), st);

@@ -53,7 +53,7 @@ struct GemmMulti {
     float *stats[3];
     // backward twin of `stats`: Y is the gradient entering a BatchNorm (+ ReLU) whose input was bnx (m,n); the epilogue
     // leaves per-row-block records [2][n] of sum g' and sum g' * xhat (g' = Y masked by the ReLU) in brec -- the reduce
-    // pass of that BatchNorm's backward (dense.hip: bn_bwd_reduce_kernel) without its own launch and its two tensor reads
+    // pass of that BatchNorm's backward (bn.hip: bn_bwd_reduce_kernel) without its own launch and its two tensor reads
     const float *bnx, *bnm, *bnr, *bng, *bnb;
     int bnrelu;
     float *brec;
@@ -714,9 +714,9 @@ static bool ksplit_ok(int m, int n, int k, bool has_records) {
     // measured and rejected as the default (round 6, profiles/r06_rejected/gemm_ksplit.md): 7x the workgroups of the 64-row form
     // but 16-20 us per launch against 11-14 (4x the weight reads per row, an LDS reduce and a barrier per workgroup), +0.45 ms a
     // step.  AO_AMD_GEMM_KSPLIT=1 turns it on for A/B runs and keeps it under test.
-    static const bool on = [] { const char *e = getenv("AO_AMD_GEMM_KSPLIT"); return e && e[0] == '1'; }();
-    const char *e = getenv("AO_AMD_GEMM");  // (lds / direct: the A/B switches of the older forms)
-    if (!on || e || ptv2_matmul_bf16()) return false;
+    static const bool on = ptv2_env_is("AO_AMD_GEMM_KSPLIT", '1');
+    // (AO_AMD_GEMM = lds / direct: the A/B switches of the older forms)
+    if (!on || ptv2_env_set("AO_AMD_GEMM") || ptv2_matmul_bf16()) return false;
     if (has_records && !g_rb16_ok) return false;  // (the public launchers' records are per 64 rows: include/ptv2_hip.h)
     return m >= 1 && m <= 32768 && (k == 96 || k == 192 || k == 384) && n % 16 == 0 && n >= 16;
 }

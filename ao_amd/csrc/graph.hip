@@ -107,8 +107,7 @@ long long now_ns() {
 int mode() {
     int m = g_mode.load(std::memory_order_relaxed);
     if (m < 0) {
-        const char *e = getenv("AO_AMD_GRAPH");
-        m = (e && e[0] == '0') ? 0 : 1;
+        m = ptv2_env_is("AO_AMD_GRAPH", '0') ? 0 : 1;
         g_mode.store(m, std::memory_order_relaxed);
     }
     return m;
@@ -117,7 +116,6 @@ int mode() {
 }  // namespace
 
 int ptv2_graph_capturing(void) { return g_inside; }
-void ptv2_profile_scope(int which, int end, int ring_entry, int ring_size);  // abi.hip
 
 namespace {
 __global__ __launch_bounds__(256) void zero_kernel(float4 *__restrict__ p, long long n4, float *__restrict__ tail, int ntail) {
@@ -196,8 +194,7 @@ PtvGraphScope::PtvGraphScope(void *stream, int which_, bool allow)
         // the call (a loop that reads the loss back every iteration -- pointcept's InformationWriter -- pays that at every
         // step, any loop at its first step behind a synchronisation: the first timed step of the bench was 11.6 ms against
         // 9.85).  Same kernels, same arguments, same order either way.  AO_AMD_GRAPH_IDLE_EAGER=0: always the graph.
-        const char *e = getenv("AO_AMD_GRAPH_IDLE_EAGER");
-        if (!(e && e[0] == '0')) {
+        if (!ptv2_env_is("AO_AMD_GRAPH_IDLE_EAGER", '0')) {
             hipEvent_t last = nullptr;
             {
                 std::lock_guard<std::mutex> lk(g_mu);
@@ -308,7 +305,7 @@ int PtvGraphScope::finish(int rc) {
         }
         const long long t1b = now_ns();
         bool ready = false;
-        static const bool debug = [] { const char *e = getenv("AO_AMD_GRAPH_DEBUG"); return e && e[0] == '1'; }();
+        static const bool debug = ptv2_env_is("AO_AMD_GRAPH_DEBUG", '1');
         if (slot.exec && slot.nodes == nodes) {
             hipGraphExecUpdateResult res = hipGraphExecUpdateSuccess;
             hipGraphNode_t bad = nullptr;

@@ -278,10 +278,6 @@ struct Ws {
 
 }  // namespace
 
-extern "C" size_t segment_minmax_hip_workspace_bytes(int b);
-extern "C" int segment_minmax_hip_launcher(int b, const float *xyz, const int *offset, float *lo, float *hi,
-                                           void *workspace, size_t workspace_bytes, void *stream);
-
 static Ws carve(void *base, int n, int b) {
     Ws w;
     char *p = (char *)base;
@@ -375,5 +371,4 @@ extern "C" int grid_pool_hip_launcher(int n, int b, const float *coord, const in
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
 }
-
 

@@ -16,7 +16,7 @@
 //                  chunks), and the folded-BN_p parameter gradients (ga, gb) as per-wave partials.
 //   bwd_rows       one lane per slot: softmax backward, Linear(G,G) backward, ReLU, BN_w affine backward;
 //                  writes gW1 and the two (N*K,G) operands (gz, y) of the Ww2 weight gradient, which is
-//                  then the same split-K MFMA reduction as any Linear (dense.hip); gsc / gsh partials.
+//                  then the same split-K MFMA reduction as any Linear (wgrad.hip); gsc / gsh partials.
 //   bwd_gv         grad v through the inverse neighbour table (fixed-order gather, no atomics).
 #include <algorithm>
 #include <cstdlib>
@@ -498,44 +498,13 @@ constexpr int BWD_TILE_BLOCKS = 256 * 16;
 
 using namespace gva;
 
-#define GVA_DISPATCH_G(g, CALL)            \
-    switch (g) {                           \
-        case 6: { CALL(6); break; }        \
-        case 12: { CALL(12); break; }      \
-        case 24: { CALL(24); break; }      \
-        case 48: { CALL(48); break; }      \
-        case 64: { CALL(64); break; }      \
-        default: return PTV2_ERR_ARG;      \
-    }
-
-extern "C" size_t gva_workspace_bytes(int n, int k, int c, int g);
-extern "C" size_t dense_workspace_bytes(int n, int cout, int cin);
-extern "C" int linear_wgrad_hip_launcher(int n, int cout, int cin, const float *gY, const float *X, float *dW,
-                                         float *db, void *workspace, size_t workspace_bytes, void *stream);
-
-// gva_bwd_point.hip: the fused MFMA backward (one launch) for the (k, c, g) it is instantiated for
-int gva_bwd_point_supported(int k, int c, int g);
-size_t gva_bwd_point_part_floats(int c, int g);
-int gva_bwd_point_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                         const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
-                         const float *g_out, const float *g_A, const float *g_sw, float *gW1, float *gsc, float *gsh,
-                         float *gWw2, float *gbw2, float *ga, float *gb, float *part, size_t part_floats_avail,
-                         hipStream_t st, const float *Wp2, const float *bp2, PtvDrop drop);
-int gva_bwd_point_local(int k, int c, int g);
-// gva_bwd_tile.hip: the deep levels' backward per tile of points, g_A formed in the kernel
-int gva_bwd_tile_supported(int k, int c, int g);
-size_t gva_bwd_tile_part_floats(int n, int c, int g);
-int gva_bwd_tile_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                        const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
-                        const float *g_out, const float *Wp2, const float *bp2, float *gW1, float *gsc, float *gsh, float *gWw2,
-                        float *gbw2, float *ga, float *gb, float *part, size_t part_floats_avail, gva::PtvDrop drop, hipStream_t st);
 // 1 when the backward of this shape runs the tile kernel (AO_AMD_BWD_POINT: the point kernel behind a peb_bwd launch instead)
+// AO_AMD_BWD_STAGED (the A/B switch of the tests, read on every call): the staged launches instead of every fused form of the
+// attention -- here, in gva_bwd.hip, gva_block.hip and the MFMA / point forms of the logits forward (gva_fwd.hip)
+bool gva_bwd_staged() { return ptv2_env_set("AO_AMD_BWD_STAGED"); }
 int gva_bwd_tile_path(int k, int c, int g) {
-    return gva_bwd_tile_supported(k, c, g) && !getenv("AO_AMD_BWD_STAGED") && !getenv("AO_AMD_BWD_POINT");
+    return gva_bwd_tile_supported(k, c, g) && !gva_bwd_staged() && !ptv2_env_set("AO_AMD_BWD_POINT");
 }
-
-int gva_softmax_point_launch(int n, int k, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                             const float *bw2, const int *idx, float *w, float *sw, hipStream_t st, PtvDrop drop);
 
 static size_t agg_part_bytes(int n, int k, int c, int g) {
     return align_up(sizeof(float) * std::max({(size_t)BWD_TILE_BLOCKS * 4 * c, (size_t)MAX_BLOCKS * 2 * g, gva_bwd_point_part_floats(c, g),
@@ -560,7 +529,7 @@ extern "C" int gva_aggregate_forward_hip_launcher(int n, int k, int c, int g, co
     const int nb_rows = (int)std::min<long long>((rows + TPB - 1) / TPB, MAX_BLOCKS * 4);
     {
         PtvScopedTimer t(KID_SOFTMAX_ROWS, st, 4.0 * ((double)rows * (2 * g + 1) + (double)n * g));
-        if (k <= 16 && (g == 12 || g == 24 || g == 48 || g == 64) && !getenv("AO_AMD_BWD_STAGED")) {  // g = 6: rows
+        if (k <= 16 && (g == 12 || g == 24 || g == 48 || g == 64) && !gva_bwd_staged()) {  // g = 6: rows
             const int rc = gva_softmax_point_launch(n, k, g, W1, sc, sh, Ww2, bw2, idx, w, sw, st, ptv2_attn_drop_current());
             if (rc != PTV2_OK) return rc;
         } else {
@@ -625,7 +594,7 @@ static int aggregate_backward_impl(int n, int k, int c, int g, const float *W1, 
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
     }
-    if (inv_ptr && gva_bwd_point_supported(k, c, g) && !getenv("AO_AMD_BWD_STAGED")) {
+    if (inv_ptr && gva_bwd_point_supported(k, c, g) && !gva_bwd_staged()) {
         // one fused MFMA launch (+ its finalize) instead of tile / rows / finalizes / the G x G weight-gradient GEMM
         {
             // W1, idx, coord, g_out, g_sw, v rows (unique once), g_A in; gW1 out

@@ -255,83 +255,12 @@ inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 
 using namespace gva;
 
-extern "C" {
-size_t gva_workspace_bytes(int n, int k, int c, int g);
-size_t gva_aggregate_workspace_bytes(int n, int k, int c, int g);
-size_t dense_workspace_bytes(int n, int cout, int cin);
-int gva_fold_p_forward_hip_launcher(int, const float *, const float *, const float *, const float *, const double *,
-                                    const double *, float *, float *, long long *, int, double, float, float, float *,
-                                    float *, float *, void *);
-int gva_fold_p_backward_hip_launcher(int, const float *, const float *, const float *, const double *, const double *,
-                                     const float *, const float *, int, const float *, const float *, float *, float *,
-                                     float *, float *, void *);
-int gva_fold_w_forward_hip_launcher(int, const double *, const double *, const float *, const float *, float *, float *,
-                                    long long *, int, double, float, float, float *, float *, double *, double *, void *);
-int gva_fold_w_backward_hip_launcher(int, const float *, const double *, const double *, int, double, const float *,
-                                     const float *, double *, double *, float *, float *, void *);
-int skinny_linear_forward_hip_launcher(int, int, int, const float *, const float *, float *, void *);
-int skinny_linear_backward_hip_launcher(int, int, int, const float *, const float *, float *, void *);
-int linear_wgrad_hip_launcher(int, int, int, const float *, const float *, float *, float *, void *, size_t, void *);
-int linear_wgrad_strided_rowscale(int, int, int, int, const float *, long long, long long, const float *, long long, long long,
-                                  float *, float *, const float *, long long, int *, void *, size_t, void *);
-int linear_wgrad_strided_hip_launcher(int, int, int, int, const float *, long long, long long, const float *, long long,
-                                      long long, float *, float *, void *, size_t, void *);
-int gva_logits_forward_hip_launcher(int, int, int, int, const float *, const float *, const float *, const float *,
-                                    const float *, const float *, const float *, const int *, float *, double *, double *,
-                                    void *, size_t, void *);
-int gva_logits_backward_hip_launcher(int, int, int, int, const float *, const float *, const float *, const float *,
-                                     const int *, const float *, const float *, const double *, const double *,
-                                     const int *, const int *, float *, float *, float *, float *, float *, float *, void *,
-                                     size_t, void *);
-int gva_aggregate_forward_hip_launcher(int, int, int, int, const float *, const float *, const float *, const float *,
-                                       const float *, const float *, const float *, const float *, const float *,
-                                       const int *, float *, float *, float *, float *, void *);
-int gva_aggregate_backward_hip_launcher(int, int, int, int, const float *, const float *, const float *, const float *,
-                                        const float *, const float *, const float *, const float *, const float *,
-                                        const int *, const float *, const float *, const float *, const float *,
-                                        const int *, const int *, float *, float *, float *, float *, float *, float *,
-                                        float *, float *, void *, size_t, void *);
-int gva_peb_forward_hip_launcher(int, int, int, const float *, const float *, const float *, const float *, const float *,
-                                 float *, void *);
-int gva_peb_backward_hip_launcher(int, int, int, const float *, const float *, const float *, float *, float *, void *);
-}
-
-int gva_logits_forward_fold(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
-                            const float *M, const float *cW, const float *coord, const int *idx, float *W1, double *T1, double *T2,
-                            const gva::FoldWFwdArgs &F, void *workspace, size_t workspace_bytes, void *stream);
-int skinny_linear_forward_pair(int n, int cin, int cout, const float *const *x, const float *W, const float *const *xsc,
-                               const float *const *xsh, float *const *y, void *stream);
-int skinny_backward_pair_bn_reduce(int n, int cin, int cout, const float *const *gy, const float *W, float *const *gx, void *stream);
-int gva_bwd_point_local(int k, int c, int g);
-int gva_bwd_tile_path(int k, int c, int g);
-int gva_fwd_point_supported(int k, int c, int g);
-int gva_fwd_point_max_n();
-int gva_fwd_point_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                         const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
-                         const float *Wp2, const float *bp2, float *w, float *sw, float *A, float *out, float *stats,
-                         void *stream);
-int gva_fwd_tile_supported(int k, int c, int g);
-int gva_wp2_wgrad_recompute(int n, int k, int c, int g, const float *g_out, const float *w, const float *sw, const float *a,
-                            const float *b, const float *coord, const int *idx, float *dW, float *db, void *workspace,
-                            size_t workspace_bytes, void *stream);
 // the deep levels' one-launch forward (gva_fwd_tile.hip) is the path of this shape; AO_AMD_FWD_STAGED: the three staged launches
-static bool gva_tile_path(int k, int c, int g) { return gva_fwd_tile_supported(k, c, g) && !getenv("AO_AMD_FWD_STAGED"); }
+static bool gva_fwd_staged() { return ptv2_env_set("AO_AMD_FWD_STAGED"); }
+static bool gva_tile_path(int k, int c, int g) { return gva_fwd_tile_supported(k, c, g) && !gva_fwd_staged(); }
 // 1 when the forward of this shape writes A (n, g, c) for the backward (block.hip sizes the saved buffer with it): the
 // staged launches, the full-resolution point kernel, or the tile path with AO_AMD_TILE_KEEP_A (the A-reading weight gradient)
-int gva_block_keeps_A(int k, int c, int g) { return !gva_tile_path(k, c, g) || getenv("AO_AMD_TILE_KEEP_A") != nullptr; }
-int gva_fwd_tile_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                        const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
-                        const float *Wp2, const float *bp2, float *w, float *sw, float *out, float *stats, float *a_out, void *stream);
-int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
-                              const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
-                              const gva::FoldWBwdArgs &F, const int *inv_ptr, const int *inv_rows, float *gkW, float *gqW, float *ga,
-                              float *gb, float *gM, float *gcW, void *workspace, size_t workspace_bytes, void *stream);
-int gva_aggregate_backward_fused_peb(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
-                                     const float *Ww2, const float *bw2, const float *v, const float *a, const float *b,
-                                     const float *coord, const int *idx, const float *w, const float *g_out, const float *Wp2,
-                                     const float *bp2, const int *inv_ptr, const int *inv_rows, float *gW1, float *gsc,
-                                     float *gsh, float *gWw2, float *gbw2, float *gv, float *ga, float *gb, void *workspace,
-                                     size_t workspace_bytes, void *stream);
+int gva_block_keeps_A(int k, int c, int g) { return !gva_tile_path(k, c, g) || ptv2_env_set("AO_AMD_TILE_KEEP_A"); }
 
 namespace {
 struct BlockWs {  // carve the block workspace
@@ -355,7 +284,7 @@ BlockWs carve(void *base, int n, int k, int c, int g) {
     w.out_v = (float *)take(sizeof(float) * (size_t)n * c);
     // (g_A (n,g,c) / g_sw only where a peb_bwd launch hands them to the aggregation backward: not at the full-resolution level's
     // point kernel nor on the deep levels' tile path, which form them on chip)
-    const bool fused_peb = (gva_bwd_point_local(k, c, g) && !getenv("AO_AMD_BWD_STAGED")) || gva_bwd_tile_path(k, c, g);
+    const bool fused_peb = (gva_bwd_point_local(k, c, g) && !gva_bwd_staged()) || gva_bwd_tile_path(k, c, g);
     w.gA = fused_peb ? nullptr : (float *)take(sizeof(float) * (size_t)n * g * c);
     w.g_sw = fused_peb ? nullptr : (float *)take(sizeof(float) * (size_t)n * g);
     w.gW1 = (float *)take(sizeof(float) * rows * g);
@@ -456,11 +385,6 @@ int gva_fold_forward_batched(int count, const ptv2_gva_block *blocks, void *stre
     return PTV2_OK;
 }
 
-int gva_peb_forward_stats(int n, int c, int g, const float *A, const float *Wp2, const float *bp2, const float *sw,
-                          const float *out_v, float *out, float *stats, int *stats_done, void *stream);
-int gva_block_forward_stats(const ptv2_gva_block *B, float *out_stats, int *stats_done, void *workspace, size_t workspace_bytes,
-                            void *stream);
-
 extern "C" int gva_block_forward_hip_launcher(const ptv2_gva_block *B, void *workspace, size_t workspace_bytes,
                                               void *stream) {
     return gva_block_forward_stats(B, nullptr, nullptr, workspace, workspace_bytes, stream);
@@ -499,7 +423,7 @@ int gva_block_forward_stats(const ptv2_gva_block *B, float *out_stats, int *stat
                                 W.stage, W.stage_bytes, stream));
     // softmax, aggregation and the grouped projection: one launch at the full-resolution level (gva_fwd_point.hip), else three
     if (gva_fwd_point_supported(k, c, g) && n <= gva_fwd_point_max_n() && !gva::ptv2_attn_drop_current().thresh &&
-        !getenv("AO_AMD_FWD_STAGED")) {
+        !gva_fwd_staged()) {
         RUN(gva_fwd_point_launch(n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, B->Wp2, B->bp2,
                                  B->w, B->sw, B->A, B->out, out_stats, stream));
         if (out_stats && stats_done) *stats_done = 64;
@@ -537,7 +461,7 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
         W.ga2 = p; p += 3 * (size_t)c;
         W.gb2 = p;
     }
-    // inside a model backward that defers weight gradients (dense.hip: WgradJob; the caller kept g_out): gkW / gqW, the operands
+    // inside a model backward that defers weight gradients (wgrad.hip: WgradJob; the caller kept g_out): gkW / gqW, the operands
     // of the kW / qW weight gradient, go to the deferral arena too (its results already live in the per-Block glue region)
     bool kq_kept = false;
     if (g_fold_scratch && ptv2_wgrad_defer_armed_rs()) {
@@ -550,7 +474,7 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
     PtvRiderGuard riders;  // an error return below must not leave queued sums (pointers into this call's workspace) behind
     // 1. projection after the neighbour sum: g_A, g_sw (formed inside the point kernel for the narrow instances),
     //    grad Wp2 (direct part), grad bp2 (direct part)
-    const bool fused_peb = (gva_bwd_point_local(k, c, g) && !getenv("AO_AMD_BWD_STAGED")) || gva_bwd_tile_path(k, c, g);
+    const bool fused_peb = (gva_bwd_point_local(k, c, g) && !gva_bwd_staged()) || gva_bwd_tile_path(k, c, g);
     if (fused_peb && !G->inv_ptr) return PTV2_ERR_ARG;  // (the fused forms gather grad v through the inverse neighbour table)
     if (!fused_peb) RUN(gva_peb_backward_hip_launcher(n, c, g, G->g_out, B->Wp2, B->bp2, W.gA, W.g_sw, stream));
     int bp2_done = 0;
@@ -612,7 +536,7 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
     {
         const float *gys[2] = {W.gkW, W.gqW};
         float *gxs[2] = {G->gk, G->gq};
-        // (+ the reduce records of the linear_q / linear_k BatchNorm backward when the Block runtime asked for them: dense.hip)
+        // (+ the reduce records of the linear_q / linear_k BatchNorm backward when the Block runtime asked for them: skinny.hip)
         RUN(skinny_backward_pair_bn_reduce(n, c, g, gys, B->Ww1, gxs, stream));
     }
     ptv2_rider_flush(st);  // anything still queued (paths without a carrying launch) before the glue reads the sums

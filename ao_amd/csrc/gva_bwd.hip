@@ -248,40 +248,9 @@ __global__ __launch_bounds__(TPB) void logits_bwd_params_kernel(int n, int k, in
     }
 }
 
-
-
 }  // namespace gva
 
 using namespace gva;
-
-int gva_bwd_point_supported(int k, int c, int g);
-int gva_logits_bwd_fused_supported(int k, int c, int g);
-int gva_logits_bwd_fused_launch(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
-                                const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
-                                const gva::FoldWBwdArgs &F, float *gWt, float *part, size_t part_floats_avail, float *gM, float *ga,
-                                float *gb, float *gcW, hipStream_t st);
-int gva_logits_params_point_launch(int n, int k, int c, int g, const float *a, const float *b, const float *M,
-                                   const float *coord, const int *idx, const float *gWt, float *part, int max_blocks,
-                                   int *nblk_out, hipStream_t st);
-
-#define GVA_DISPATCH_G(g, CALL)            \
-    switch (g) {                           \
-        case 6: { CALL(6); break; }        \
-        case 12: { CALL(12); break; }      \
-        case 24: { CALL(24); break; }      \
-        case 48: { CALL(48); break; }      \
-        case 64: { CALL(64); break; }      \
-        default: return PTV2_ERR_ARG;      \
-    }
-
-extern "C" size_t gva_workspace_bytes(int n, int k, int c, int g);
-
-// F.gsc != NULL: gT1 / gT2 are not read; the rows kernel derives them from the fold_w backward (and writes the BatchNorm's
-// parameter gradients) -- internal to the block runtime (gva_block.hip)
-int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
-                              const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
-                              const gva::FoldWBwdArgs &F, const int *inv_ptr, const int *inv_rows, float *gkW, float *gqW, float *ga,
-                              float *gb, float *gM, float *gcW, void *workspace, size_t workspace_bytes, void *stream);
 
 extern "C" int gva_logits_backward_hip_launcher(int n, int k, int c, int g, const float *a, const float *b,
                                                 const float *M, const float *coord, const int *idx,
@@ -305,9 +274,8 @@ int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const 
     float *part = (float *)workspace;
     float *gWt = (float *)((char *)workspace + rows_offset_bytes(c, g));
     // wide-group levels: rows + parameter gradients in one pipelined MFMA launch (gva_bwd_logits.hip), then the gather
-    const char *lb = getenv("AO_AMD_LOGITS_BWD");  // "staged": the three-kernel form (A/B switch of the tests)
-    const bool fused_off = lb && lb[0] == 's';
-    if (inv_ptr && gva_logits_bwd_fused_supported(k, c, g) && !fused_off && !getenv("AO_AMD_BWD_STAGED")) {
+    const bool fused_off = ptv2_env_is("AO_AMD_LOGITS_BWD", 's');  // "staged": the three-kernel form (A/B switch of the tests)
+    if (inv_ptr && gva_logits_bwd_fused_supported(k, c, g) && !fused_off && !gva_bwd_staged()) {
         {
             // W1, gW1 in, gWt out, idx, coord; parameter-sized outputs
             PtvScopedTimer t(KID_LOGITS_BWD_FUSED + (g == 6 ? 0 : g == 12 ? 1 : g == 24 ? 2 : g == 48 ? 3 : 4), st,
@@ -344,7 +312,7 @@ int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const 
     const size_t comb_bytes = sizeof(float) * (size_t)nsl * cbk * (g + 4);
     // enough workgroups to hide the tile-load latency (8 per CU), bounded by the partial-sum budget
     const int par_cap = (int)std::max<long long>(64, std::min<long long>(MAX_BLOCKS, ((long long)MAX_PARAM_BLOCKS * 24576) / ((long long)c * (g + 4))));
-    if (g >= 48 && gva_bwd_point_supported(k, c, g) && !getenv("AO_AMD_BWD_STAGED")) {  // pays for wide G only
+    if (g >= 48 && gva_bwd_point_supported(k, c, g) && !gva_bwd_staged()) {  // pays for wide G only
         int nb = 0;
         {
             PtvScopedTimer t(KID_LOGITS_BWD_PARAMS, st, 4.0 * ((double)rows * (g + 1) + 3.0 * n));

@@ -21,8 +21,6 @@
 
 #include "gva_common.h"
 
-int gva_bwd_point_local(int k, int c, int g);
-
 namespace gva {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -1115,8 +1113,6 @@ int launch_params_point(int n, int k, const float *a, const float *b, const floa
     *nblk_out = nblk;
     return PTV2_OK;
 }
-
-
 
 template <int G, int C, int NW>
 int launch_bwd_point(int n, int k, const float *W1, const float *sc, const float *sh, const float *Ww2, const float *bw2,

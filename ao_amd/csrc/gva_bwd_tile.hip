@@ -586,7 +586,7 @@ static int bwd_tile_full_rounds(int n) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)attention_bwd_tile_mixed_kernel<G, C, false>, 256, lds) != hipSuccess || occ < 1) occ = 2;
         slots = occ * cus;
     }
-    static const bool off = [] { const char *e = getenv("AO_AMD_BT_MIXED"); return e && e[0] == '0'; }();
+    static const bool off = ptv2_env_is("AO_AMD_BT_MIXED", '0');
     const int nt8 = (n + 7) / 8, full = nt8 / slots * slots, tail = nt8 - full;
     return (!off && full > 0 && tail > 0 && 2 * tail <= slots) ? full : 0;
 }

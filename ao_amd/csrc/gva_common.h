@@ -605,3 +605,14 @@ static __global__ __launch_bounds__(1024) void finalize_logit_sums_kernel(const 
 }
 
 }  // namespace gva
+
+// host-side dispatch of a launcher body on the number of groups
+#define GVA_DISPATCH_G(g, CALL)            \
+    switch (g) {                           \
+        case 6: { CALL(6); break; }        \
+        case 12: { CALL(12); break; }      \
+        case 24: { CALL(24); break; }      \
+        case 48: { CALL(48); break; }      \
+        case 64: { CALL(64); break; }      \
+        default: return PTV2_ERR_ARG;      \
+    }

@@ -276,24 +276,6 @@ extern "C" int gva_pos_moments_hip_launcher(int n, int k, const float *coord, co
     return PTV2_OK;
 }
 
-#define GVA_DISPATCH_G(g, CALL)            \
-    switch (g) {                           \
-        case 6: { CALL(6); break; }        \
-        case 12: { CALL(12); break; }      \
-        case 24: { CALL(24); break; }      \
-        case 48: { CALL(48); break; }      \
-        case 64: { CALL(64); break; }      \
-        default: return PTV2_ERR_ARG;      \
-    }
-
-int gva_logits_fwd_mfma_supported(int k, int c, int g);
-int gva_logits_fwd_mfma_launch(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
-                               const float *M, const float *cW, const float *coord, const int *idx, float *W1, float *part,
-                               double *T1, double *T2, const gva::FoldWFwdArgs &F, hipStream_t st);
-int gva_logits_point_launch(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
-                            const float *M, const float *cW, const float *coord, const int *idx, float *W1, float *part,
-                            double *T1, double *T2, const gva::FoldWFwdArgs &F, hipStream_t st);
-
 // F.sc != NULL: the final reduction also folds BN_w (block runtime); the C entry point below passes none
 int gva_logits_forward_fold(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
                             const float *M, const float *cW, const float *coord, const int *idx, float *W1, double *T1, double *T2,
@@ -304,7 +286,7 @@ int gva_logits_forward_fold(int n, int k, int c, int g, const float *kW, const f
     float *part = (float *)workspace;
     const long long rows = (long long)n * k;
     {
-        if (gva_logits_fwd_mfma_supported(k, c, g) && !getenv("AO_AMD_BWD_STAGED")) {
+        if (gva_logits_fwd_mfma_supported(k, c, g) && !gva_bwd_staged()) {
             PtvScopedTimer t(KID_LOGITS_FWD, st, 4.0 * ((double)n * k * (g + 1) + (double)n * (3 + 2 * g)));
             const int rc = gva_logits_fwd_mfma_launch(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st);
             if (rc != PTV2_OK) return rc;
@@ -312,7 +294,7 @@ int gva_logits_forward_fold(int n, int k, int c, int g, const float *kW, const f
             return PTV2_OK;
         }
     }
-    if (k <= 16 && c % 4 == 0 && (g == 48 || g == 64) && !getenv("AO_AMD_BWD_STAGED")) {  // pays for wide G only
+    if (k <= 16 && c % 4 == 0 && (g == 48 || g == 64) && !gva_bwd_staged()) {  // pays for wide G only
         PtvScopedTimer t(KID_LOGITS_FWD, st, 4.0 * ((double)n * k * (g + 1) + (double)n * (3 + 2 * g)));
         const int rc = gva_logits_point_launch(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st);
         if (rc != PTV2_OK) return rc;

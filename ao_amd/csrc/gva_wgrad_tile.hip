@@ -13,7 +13,7 @@
 // points, 4 matrix instructions per point and 16 channels, w^T read straight into the operand layout) and parks them in LDS;
 // phase B contracts over the tile's 16 points, out^T (i, c') += g_out^T (i, p) A (p, c'), 4 matrix instructions per group and
 // 16 channels.  Every workgroup leaves one partial record in the layout of the strided weight gradient ([g][8][c] weights,
-// then [g][8] bias sums), so the finalize of dense.hip (per call, or batched over the deferred jobs of a backward) sums them
+// then [g][8] bias sums), so the finalize of wgrad.hip (per call, or batched over the deferred jobs of a backward) sums them
 // in a fixed order.
 #include <algorithm>
 #include <cstdlib>

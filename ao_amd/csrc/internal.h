@@ -1,0 +1,142 @@
+// ao_amd/csrc/internal.h -- the library's internal interface: every function that one .hip unit defines and another calls
+// and that include/ptv2_hip.h does not declare, once, under the unit that defines it.  common.h includes it, so the defining
+// unit sees the declaration too and the compiler checks the two against each other (an extern "C" symbol carries no
+// signature: nothing else would).  Types taken by reference or value are only named here; gva_common.h and wgrad_job.h,
+// which the callers include, define them.  (common.h and gva_common.h keep the interfaces that sit next to their types.)
+#pragma once
+
+namespace gva { struct FoldWFwdArgs; struct FoldWBwdArgs; struct PtvDrop; }
+namespace dense { struct WgradJob; }
+
+// ---- abi.hip ----------------------------------------------------------------------------------------------------------
+void ptv2_profile_scope(int which, int end, int ring_entry, int ring_size);
+// ---- gemm.hip ---------------------------------------------------------------------------------------------------------
+// rows per statistics / reduce record the fused row GEMMs write for a shape (16: the deep levels' k-split kernel),
+// and the switch that tells them this caller reads either
+int rows_gemm_record_rows(int m, int n, int k);
+void ptv2_gemm_allow_rb16(int on);
+// ---- bn.hip -----------------------------------------------------------------------------------------------------------
+size_t bn_tiles_floats_rb(int n, int c, int rb);  // floats of a statistics record buffer with records of rb rows each
+int bn_tiles_finalize_rb(int n, int c, int rb, float *part, const float *gamma, const float *beta, float *mean, float *rstd,
+                         float *sc, float *sh, float *running_mean, float *running_var, long long *num_batches_tracked, float eps,
+                         float momentum, void *stream);
+int bn_tiles_finalize_pair(int n, int c, float *const *part, const float *const *gamma, const float *const *beta,
+                           float *const *mean, float *const *rstd, float *const *sc, float *const *sh, float *const *running_mean,
+                           float *const *running_var, long long *const *num_batches_tracked, float eps, float momentum,
+                           void *stream, int rb);
+int bn_tiles_apply_residual(int n, int c, float *part, const float *gamma, const float *beta, float *mean, float *rstd, float *sc,
+                            float *sh, float *running_mean, float *running_var, long long *num_batches_tracked, float eps,
+                            float momentum, const float *x, const float *residual, const float *rowscale, float *y, void *stream,
+                            int rb);
+int bn_tiles_apply_relu(int n, int c, float *part, const float *gamma, const float *beta, float *mean, float *rstd,
+                        float *running_mean, float *running_var, long long *num_batches_tracked, float eps, float momentum,
+                        const float *x, float *y, void *stream);
+// ---- skinny.hip -------------------------------------------------------------------------------------------------------
+int skinny_linear_forward_pair(int n, int cin, int cout, const float *const *x, const float *W, const float *const *xsc,
+                               const float *const *xsh, float *const *y, void *stream);
+// the q / k BatchNorms' reduce inside the skinny input-gradient launch: armed by block.hip, run by gva_block.hip, and the
+// BatchNorm pair launcher (bn.hip) takes the count of records it left (0: none)
+void ptv2_skinny_bn_arm(int n, int c, const float *const *x, const float *const *gy, const float *const *mean,
+                        const float *const *rstd, const float *const *gamma, const float *const *beta, int relu, void *workspace,
+                        size_t workspace_bytes);
+void ptv2_skinny_bn_disarm(void);
+int skinny_backward_pair_bn_reduce(int n, int cin, int cout, const float *const *gy, const float *W, float *const *gx,
+                                   void *stream);
+int ptv2_skinny_bn_take_records(int n, int c, const float *part, const float *const *gy);
+// ---- wgrad.hip --------------------------------------------------------------------------------------------------------
+// linear_wgrad_strided_hip_launcher with rowscale != NULL asking for db[b][o] = sum_n gY[n, b, o] * rowscale[n * lds_s + b]
+// instead of the plain column sums.  Only the LDS-staged fp32 kernel forms them: *weighted says whether it did (1) or
+// whether the caller has to compute db itself (0: db is then not written at all).
+extern "C" int linear_wgrad_strided_rowscale(int n, int cout, int cin, int batch, const float *gY, long long ldy, long long sy,
+                                             const float *X, long long ldx, long long sx, float *dW, float *db,
+                                             const float *rowscale, long long lds_s, int *weighted, void *workspace,
+                                             size_t workspace_bytes, void *stream);
+int gva_wp2_wgrad_recompute(int n, int k, int c, int g, const float *g_out, const float *w, const float *sw, const float *a,
+                            const float *b, const float *coord, const int *idx, float *dW, float *db, void *workspace,
+                            size_t workspace_bytes, void *stream);
+// ---- block.hip --------------------------------------------------------------------------------------------------------
+int ptv2_blocks_fold_forward(int count, const ptv2_block *blocks, void *stream);
+// ---- gva_block.hip ----------------------------------------------------------------------------------------------------
+int gva_block_keeps_A(int k, int c, int g);
+int gva_fold_forward_batched(int count, const ptv2_gva_block *blocks, void *stream);
+int gva_block_forward_stats(const ptv2_gva_block *B, float *out_stats, int *stats_done, void *workspace, size_t workspace_bytes,
+                            void *stream);
+void ptv2_gva_set_prefolded(int on);
+size_t ptv2_gva_fold_scratch_floats(int c, int g);  // deferred M / cW glue of the attention backward
+void ptv2_gva_set_fold_scratch(float *p);
+int ptv2_gva_flush_folds(void *stream);
+void ptv2_gva_drop_folds();
+// ---- gva_fwd.hip ------------------------------------------------------------------------------------------------------
+int gva_logits_forward_fold(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
+                            const float *M, const float *cW, const float *coord, const int *idx, float *W1, double *T1, double *T2,
+                            const gva::FoldWFwdArgs &F, void *workspace, size_t workspace_bytes, void *stream);
+// ---- gva_fwd_point.hip ------------------------------------------------------------------------------------------------
+int gva_fwd_point_supported(int k, int c, int g);
+int gva_fwd_point_max_n();
+int gva_fwd_point_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
+                         const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
+                         const float *Wp2, const float *bp2, float *w, float *sw, float *A, float *out, float *stats, void *stream);
+// ---- gva_fwd_tile.hip -------------------------------------------------------------------------------------------------
+int gva_fwd_tile_supported(int k, int c, int g);
+int gva_fwd_tile_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
+                        const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
+                        const float *Wp2, const float *bp2, float *w, float *sw, float *out, float *stats, float *a_out,
+                        void *stream);
+// ---- gva_peb.hip ------------------------------------------------------------------------------------------------------
+int gva_peb_forward_stats(int n, int c, int g, const float *A, const float *Wp2, const float *bp2, const float *sw,
+                          const float *out_v, float *out, float *stats, int *stats_done, void *stream);
+// ---- gva_aggregate.hip ------------------------------------------------------------------------------------------------
+bool gva_bwd_staged();  // AO_AMD_BWD_STAGED is set: the staged launches in every stage of the attention
+int gva_bwd_tile_path(int k, int c, int g);
+int gva_aggregate_backward_fused_peb(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
+                                     const float *Ww2, const float *bw2, const float *v, const float *a, const float *b,
+                                     const float *coord, const int *idx, const float *w, const float *g_out, const float *Wp2,
+                                     const float *bp2, const int *inv_ptr, const int *inv_rows, float *gW1, float *gsc, float *gsh,
+                                     float *gWw2, float *gbw2, float *gv, float *ga, float *gb, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+// ---- gva_bwd.hip ------------------------------------------------------------------------------------------------------
+// F.gsc != NULL: gT1 / gT2 are not read; the rows kernel derives them from the fold_w backward (and writes the BatchNorm's
+// parameter gradients)
+int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
+                              const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
+                              const gva::FoldWBwdArgs &F, const int *inv_ptr, const int *inv_rows, float *gkW, float *gqW,
+                              float *ga, float *gb, float *gM, float *gcW, void *workspace, size_t workspace_bytes, void *stream);
+// ---- gva_bwd_logits.hip -----------------------------------------------------------------------------------------------
+int gva_logits_bwd_fused_supported(int k, int c, int g);
+int gva_logits_bwd_fused_launch(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
+                                const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
+                                const gva::FoldWBwdArgs &F, float *gWt, float *part, size_t part_floats_avail, float *gM, float *ga,
+                                float *gb, float *gcW, hipStream_t st);
+int gva_logits_fwd_mfma_supported(int k, int c, int g);
+int gva_logits_fwd_mfma_launch(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
+                               const float *M, const float *cW, const float *coord, const int *idx, float *W1, float *part,
+                               double *T1, double *T2, const gva::FoldWFwdArgs &F, hipStream_t st);
+// ---- gva_bwd_point.hip: the fused MFMA backward (one launch) for the (k, c, g) it is instantiated for -----------------
+int gva_bwd_point_supported(int k, int c, int g);
+int gva_bwd_point_local(int k, int c, int g);
+size_t gva_bwd_point_part_floats(int c, int g);
+int gva_bwd_point_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
+                         const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
+                         const float *g_out, const float *g_A, const float *g_sw, float *gW1, float *gsc, float *gsh, float *gWw2,
+                         float *gbw2, float *ga, float *gb, float *part, size_t part_floats_avail, hipStream_t st, const float *Wp2,
+                         const float *bp2, gva::PtvDrop drop);
+int gva_softmax_point_launch(int n, int k, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
+                             const float *bw2, const int *idx, float *w, float *sw, hipStream_t st, gva::PtvDrop drop);
+int gva_logits_point_launch(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
+                            const float *M, const float *cW, const float *coord, const int *idx, float *W1, float *part, double *T1,
+                            double *T2, const gva::FoldWFwdArgs &F, hipStream_t st);
+int gva_logits_params_point_launch(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
+                                   const int *idx, const float *gWt, float *part, int max_blocks, int *nblk_out, hipStream_t st);
+// ---- gva_bwd_tile.hip: the deep levels' backward per tile of points, g_A formed in the kernel -------------------------
+int gva_bwd_tile_supported(int k, int c, int g);
+size_t gva_bwd_tile_part_floats(int n, int c, int g);
+int gva_bwd_tile_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
+                        const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
+                        const float *g_out, const float *Wp2, const float *bp2, float *gW1, float *gsc, float *gsh, float *gWw2,
+                        float *gbw2, float *ga, float *gb, float *part, size_t part_floats_avail, gva::PtvDrop drop,
+                        hipStream_t st);
+// ---- gva_wgrad_tile.hip -----------------------------------------------------------------------------------------------
+int gva_wgrad_tile_supported(int k, int c, int g);
+size_t gva_wgrad_tile_plan(dense::WgradJob *J, int max_splits);
+int gva_wgrad_tile_launch_one(const dense::WgradJob &J, hipStream_t st);
+int gva_wgrad_tile_launch_jobs(const dense::WgradJob *table, int njobs, int wgs, int pos_wgs, hipStream_t st);

@@ -24,13 +24,6 @@
 
 #include "common.h"
 
-int ptv2_blocks_fold_forward(int count, const ptv2_block *blocks, void *stream);  // block.hip
-void ptv2_gva_set_prefolded(int on);                                                // gva_block.hip
-size_t ptv2_gva_fold_scratch_floats(int c, int g);  // deferred M / cW glue of the attention backward (gva_block.hip)
-void ptv2_gva_set_fold_scratch(float *p);
-int ptv2_gva_flush_folds(void *stream);
-void ptv2_gva_drop_folds();
-
 namespace {
 
 constexpr int TPB = 256;
@@ -292,7 +285,7 @@ struct Work {
     float *ga, *gb, *gc;               // gradient temporaries, max over levels of n * widest channel count
     float *gskip[PTV2_MAX_STAGES + 1]; // gradient of the encoder output at level i (two contributions)
     float *fold_scratch[PTV2_MAX_BLOCKS];    // per-Block operands of the attention's parameter glue, run once at the end
-    char *wdefer; size_t wdefer_bytes;       // deferred weight gradients (dense.hip): job table, kept operands, chunk records
+    char *wdefer; size_t wdefer_bytes;       // deferred weight gradients (wgrad.hip): job table, kept operands, chunk records
     size_t bytes;
 };
 
@@ -384,18 +377,12 @@ std::atomic<int> g_wgrad_defer_mode{-1};  // -1: read AO_AMD_WGRAD_DEFER on firs
 bool wgrad_defer_enabled() {
     int m = g_wgrad_defer_mode.load();
     if (m < 0) {
-        const char *e = getenv("AO_AMD_WGRAD_DEFER");
-        m = (e && e[0] == '0') ? 0 : 1;
+        m = ptv2_env_is("AO_AMD_WGRAD_DEFER", '0') ? 0 : 1;
         g_wgrad_defer_mode.store(m);
     }
     return m != 0;
 }
 
-}  // namespace
-int bn_tiles_apply_relu(int n, int c, float *part, const float *gamma, const float *beta, float *mean, float *rstd, float *running_mean,
-                        float *running_var, long long *num_batches_tracked, float eps, float momentum, const float *x, float *y,
-                        void *stream);  // dense.hip
-namespace {
 bool use_batch(const ptv2_model *M, const ptv2_linbn &L) { return M->training || !L.run_mean || !L.run_var; }
 
 // h = x W^T + b (row GEMM, or the narrow kernel when cin is not a multiple of 4); y = ReLU(BN(h)).  `y` may differ from
@@ -444,7 +431,7 @@ int linbn_forward(const ptv2_model *M, const ptv2_linbn &L, const LinBnSaved &S,
 // `accumulate`; gx == NULL: the input needs no gradient (the patch embedding)
 int linbn_backward(const ptv2_model *M, const ptv2_linbn &L, const LinBnSaved &S, int n, const float *x, const float *gy, float *gh,
                    float *gx, int accumulate, const Work &W, void *stream) {
-    // (weight gradients deferred, dense.hip: gh, the operand of this layer's, lives in the deferral arena until the backward ends)
+    // (weight gradients deferred, wgrad.hip: gh, the operand of this layer's, lives in the deferral arena until the backward ends)
     float *kept = ptv2_wgrad_defer_active() ? ptv2_wgrad_defer_alloc((size_t)n * L.cout) : nullptr;
     if (kept) gh = kept;
     RUN(bn_backward_hip_launcher(n, L.cout, S.h, gy, S.mean, S.rstd, L.gamma, L.beta, 1, use_batch(M, L) ? 1 : 0, gh, L.ggamma,
@@ -695,7 +682,7 @@ int model_backward(const ptv2_model *M, const float *g_logits, void *workspace, 
     int rc = PTV2_OK;
     ptv2_gva_drop_folds();  // (a previous call that failed half-way may have left entries queued)
     struct DropFolds { bool armed = true; ~DropFolds() { if (armed) ptv2_gva_drop_folds(); } } drop_folds;
-    // the Blocks' five-product weight gradients are filed and run by one launch at the end (dense.hip: WgradJob).  Not under
+    // the Blocks' five-product weight gradients are filed and run by one launch at the end (wgrad.hip: WgradJob).  Not under
     // checkpointing (their X operands live in the one shared saved region); AO_AMD_WGRAD_DEFER=0: every launch where it is called
     struct WgradDeferScope {
         WgradDeferScope(void *arena, size_t bytes, bool on) { if (on) ptv2_wgrad_defer_begin(arena, bytes); }

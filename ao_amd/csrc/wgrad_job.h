@@ -1,4 +1,4 @@
-// ao_amd/csrc/wgrad_job.h -- the record of a deferred weight-gradient launch (dense.hip: the launches of a whole backward
+// ao_amd/csrc/wgrad_job.h -- the record of a deferred weight-gradient launch (wgrad.hip: the launches of a whole backward
 // filed where they are called and run by one launch per kernel form at its end), shared with gva_wgrad_tile.hip.
 #pragma once
 

@@ -1,4 +1,4 @@
-"""Per-point dense layers of PT-v2m2 on the HIP kernels of ao_amd/csrc/dense.hip.
+"""Per-point dense layers of PT-v2m2 on the HIP kernels of ao_amd/csrc/bn.hip and wgrad.hip.
 
 `RowLinear` / `RowBatchNorm1d` subclass nn.Linear / nn.BatchNorm1d, so parameter names, buffers and
 state_dict layout are exactly the reference's; only the execution differs:
@@ -69,7 +69,7 @@ class _BNRows(torch.autograd.Function):
 
 
 class _BNResidualRelu(torch.autograd.Function):
-    """y = ReLU(identity + rowscale * BN(x)): the tail of a Block in one apply pass (dense.hip)."""
+    """y = ReLU(identity + rowscale * BN(x)): the tail of a Block in one apply pass (bn.hip)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)

@@ -12,7 +12,7 @@ the execution plan:
     composition of gather ops below (`gva_unfused`) is kept as the in-framework statement of
     the same math for debugging (AO_AMD_GVA=unfused);
   * dense per-point Linear layers run on the fp32-MFMA row GEMM of ao_amd/csrc/gemm.hip (`RowLinear`), with the
-    BatchNorm around them fused into its epilogue / operand load (ao_amd/csrc/dense.hip).
+    BatchNorm around them fused into its epilogue / operand load (ao_amd/csrc/bn.hip).
 
 Every stage module also answers the reference's own `forward` signature -- `GridPool(points, start=None) ->
 (points, cluster)`, `UnpoolWithSkip(points, skip_points, cluster=None)`, `Encoder(points) -> (points, cluster)`,

@@ -66,7 +66,7 @@ int ptv2_graph_mode(int on);
 int ptv2_graph_stats(double *out, int reset);
 int ptv2_graph_reset(void);
 /* The weight gradients of the Blocks inside ptv2_model_backward_hip_launcher are filed where they are called and run by ONE
- * launch per kernel form at the end of the backward (ao_amd/csrc/dense.hip: WgradJob; same kernels over longer row chunks: equal
+ * launch per kernel form at the end of the backward (ao_amd/csrc/wgrad.hip: WgradJob; same kernels over longer row chunks: equal
  * to ~2e-6 of a gradient's norm).
  * on = 0: every launch where it is called; 1: deferred (default; AO_AMD_WGRAD_DEFER=0 sets 0); -1: query.  Returns the previous
  * setting. */

@@ -1,4 +1,4 @@
-"""Float64 reference of the dense row kernels (ao_amd/csrc/gemm.hip, the dense part of ao_amd/csrc/dense.hip) and inputs on
+"""Float64 reference of the dense row kernels (ao_amd/csrc/gemm.hip and ao_amd/csrc/bn.hip, wgrad.hip, skinny.hip) and inputs on
 which no ReLU mask can flip.
 
 Test infrastructure (plain torch, no project kernels).  Every statement below is written from the contracts documented in
@@ -43,8 +43,8 @@ from tests.gva_ref64 import errors  # noqa: F401  (relative L2, largest element 
 EPS, MOMENTUM = 1e-5, 0.1
 
 # ---------------------------------------------------------------------------------------------------------------- dispatch rules
-# python mirrors of the launchers' shape rules (gemm.hip: column_block, launch_gemm_direct, ksplit_ok; dense.hip: wg_chunk,
-# bn_grid, finapply_ok): the case lists below are placed on both sides of every switch with them, and the tests assert that the
+# python mirrors of the launchers' shape rules (gemm.hip: column_block, launch_gemm_direct, ksplit_ok; wgrad.hip: wg_chunk;
+# dense_common.h: bn_grid; bn.hip: finapply_ok): the case lists below are placed on both sides of every switch with them, and the tests assert that the
 # cases reach every kernel family.
 BM = 64
 

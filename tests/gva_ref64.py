@@ -56,7 +56,7 @@ def _cases():
         add(n, 48, 6, k=8)
     # the tile shapes.  n on the dispatch edges of the code:
     #   1, 5, 17            a cloud shorter than K in every row; one ragged 4-, 8- and 16-point tile
-    #   127, 128, 129       n % 16 = 15, 0, 1 (gva_fwd_tile.hip); the weight gradient's split n / 128 + 1 (dense.hip)
+    #   127, 128, 129       n % 16 = 15, 0, 1 (gva_fwd_tile.hip); the weight gradient's split n / 128 + 1 (wgrad.hip)
     #   1024, 1025          the 384-wide backward: 4-point tiles while (n + 3) / 4 <= 256, 8-point tiles beyond
     #   3072, 3080, 4096, 4097, 4501, 6144, 6152, 6500
     #                       bwd_tile_full_rounds (gva_bwd_tile.hip), slots = occupancy x CUs read at run time: whole rounds only

@@ -30,7 +30,7 @@ def test_two_ranks_spawned_by_bench_py_on_one_device():
     two = _bench(["--gpus", "2"] + common, AO_AMD_BENCH_ONE_DEVICE="1", AO_AMD_BENCH_BACKEND="gloo")
     # (Round 3 retried here once on a NaN loss, seen once in 67 runs, always the first process group on a fresh box.  Root cause
     # found in round 4 in the ISA: the "last block arrives" protocol of the in-kernel reductions published its arrival without
-    # draining the block's record stores first (gva_common.h: last_block_arrives, dense.hip: bn_finalize_tiles_split_kernel),
+    # draining the block's record stores first (gva_common.h: last_block_arrives, bn.hip: bn_finalize_tiles_split_kernel),
     # so the finishing block could read a record slot's previous contents -- on a fresh process, whatever the workspace
     # held.  Fixed there; no retry: a NaN fails the test.)
     assert two["n_gpus"] == 2 and two["config"]["rccl_ranks"] == 2 and two["config"]["launcher"] == "bench.py spawn"

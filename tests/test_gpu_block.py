@@ -425,7 +425,7 @@ def test_fused_logits_backward_equals_the_staged_kernels(monkeypatch, n, c, g):
 
 @pytest.mark.parametrize("n,c,g", [(4501, 192, 24), (1074, 384, 48), (9000, 96, 12), (5000, 48, 6)])
 def test_bn_backward_finalize_in_the_apply_kernel_equals_the_three_launch_form(monkeypatch, n, c, g):
-    """dense.hip (round 3): at the deep levels the BatchNorm backward's record sum runs in the prologue of the apply kernel
+    """bn.hip (round 3): at the deep levels the BatchNorm backward's record sum runs in the prologue of the apply kernel
     (bn_bwd_finapply_kernel) instead of a finalize launch of its own -- all four BatchNorm backwards of a Block (norm3 with the
     residual tail, norm2 and norm1 from the GEMM-epilogue records, the linear_q / linear_k pair).  Against
     AO_AMD_BN_FINAPPLY=0 (reduce -> finalize -> apply): same arithmetic per element, the column sums differ in summation

@@ -1,4 +1,4 @@
-"""GPU: RowBatchNorm1d / RowLinear (ao_amd/csrc/dense.hip) against stock torch modules with the same
+"""GPU: RowBatchNorm1d / RowLinear (ao_amd/csrc/bn.hip, wgrad.hip) against stock torch modules with the same
 parameters, forward, backward and running statistics."""
 import copy
 

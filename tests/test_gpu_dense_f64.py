@@ -1,4 +1,4 @@
-"""GPU: every form of the dense row kernels (ao_amd/csrc/gemm.hip, the dense part of ao_amd/csrc/dense.hip) against float64.
+"""GPU: every form of the dense row kernels (ao_amd/csrc/gemm.hip and ao_amd/csrc/bn.hip, wgrad.hip, skinny.hip) against float64.
 
 Reference: tests/dense_ref64.py -- float64 statements of the contracts in include/ptv2_hip.h, on inputs whose ReLU masks cannot
 differ between fp32 and float64 (dyadic operands with exact zeros planted at the kink where the statistics are operands; a guard

@@ -238,7 +238,7 @@ def test_wgrad_launcher_rejects_other_shapes():
 
 
 def test_deferred_recompute_weight_gradient_has_the_same_bits():
-    """dense.hip::gva_wp2_wgrad_recompute claims "the same split as a filed job: the same bits either way".  The benchmark's
+    """wgrad.hip::gva_wp2_wgrad_recompute claims "the same split as a filed job: the same bits either way".  The benchmark's
     scene (levels of 18 905 x 96, 4 501 x 192, 1 074 x 384 points): grad of every deep level's attn.linear_p_bias.3 with the
     weight gradients filed and run batched at the end of the backward (wp2_wgrad_tile_kernel_jobs behind the posrel pre-pass;
     the default) against every launch where it is called (AO_AMD_WGRAD_DEFER=0, here through the same switch's setter
