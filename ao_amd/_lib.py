@@ -34,6 +34,7 @@ _SIGNATURES = {
     "ptv2_wgrad_defer_mode": (_c_int, [_c_int]),
     "ptv2_graph_stats": (_c_int, [ctypes.POINTER(ctypes.c_double), _c_int]),
     "ptv2_graph_reset": (_c_int, []),
+    "ptv2_gva_plan_describe": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_int), _c_int]),
     "knn_query_hip_workspace_bytes": (_c_size, [_c_int] * 3),
     "knn_query_hip_launcher": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_size, _vp]),
     "knn_query_grid_hip_launcher": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,

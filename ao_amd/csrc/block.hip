@@ -16,10 +16,9 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gva_plan.h"
 
 namespace {
-
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Saved {
     float *h1, *hq, *hk, *v, *attn, *h3;                          // (n,c) each
@@ -33,28 +32,24 @@ struct Saved {
 
 Saved carve_saved(void *base, int n, int k, int c, int g) {
     Saved s;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += al(bytes); return r; };
+    PtvCarver cv{(char *)base, 0};
     const size_t nc = sizeof(float) * (size_t)n * c, ng = sizeof(float) * (size_t)n * g;
     const size_t rows = sizeof(float) * (size_t)n * k * g;
-    s.h1 = (float *)take(nc); s.hq = (float *)take(nc); s.hk = (float *)take(nc); s.v = (float *)take(nc);
-    s.attn = (float *)take(nc); s.h3 = (float *)take(nc);
+    s.h1 = (float *)cv.take(nc); s.hq = (float *)cv.take(nc); s.hk = (float *)cv.take(nc); s.v = (float *)cv.take(nc);
+    s.attn = (float *)cv.take(nc); s.h3 = (float *)cv.take(nc);
     for (int i = 0; i < PTV2_BLK_NBN; ++i) {
-        s.mean[i] = (float *)take(sizeof(float) * c);
-        s.rstd[i] = (float *)take(sizeof(float) * c);
-        s.bsc[i] = (float *)take(sizeof(float) * c);
-        s.bsh[i] = (float *)take(sizeof(float) * c);
+        s.mean[i] = cv.take_n<float>(c); s.rstd[i] = cv.take_n<float>(c);
+        s.bsc[i] = cv.take_n<float>(c); s.bsh[i] = cv.take_n<float>(c);
     }
-    s.a = (float *)take(sizeof(float) * 3 * c); s.b = (float *)take(sizeof(float) * c);
-    s.rstd_p = (float *)take(sizeof(float) * c); s.M = (float *)take(sizeof(float) * (size_t)c * g);
-    s.cW = (float *)take(sizeof(float) * g); s.kW = (float *)take(ng); s.qW = (float *)take(ng);
+    s.a = cv.take_n<float>(3 * c); s.b = cv.take_n<float>(c);
+    s.rstd_p = cv.take_n<float>(c); s.M = cv.take_n<float>((size_t)c * g);
+    s.cW = cv.take_n<float>(g); s.kW = (float *)cv.take(ng); s.qW = (float *)cv.take(ng);
     // (A (n,g,c) only where the attention forward of this shape writes it: not at the deep levels' tile path)
-    s.W1 = (float *)take(rows); s.w = (float *)take(rows);
-    s.A = gva_block_keeps_A(k, c, g) ? (float *)take(sizeof(float) * (size_t)n * g * c) : nullptr;
-    s.sw = (float *)take(ng); s.sc = (float *)take(sizeof(float) * g); s.sh = (float *)take(sizeof(float) * g);
-    s.mean_w = (double *)take(sizeof(double) * g); s.rstd_w = (double *)take(sizeof(double) * g);
-    s.bytes = off;
+    s.W1 = (float *)cv.take(rows); s.w = (float *)cv.take(rows);
+    s.A = gva_plan(n, k, c, g, false, true).keeps_A ? cv.take_n<float>((size_t)n * g * c) : nullptr;
+    s.sw = (float *)cv.take(ng); s.sc = cv.take_n<float>(g); s.sh = cv.take_n<float>(g);
+    s.mean_w = cv.take_n<double>(g); s.rstd_w = cv.take_n<double>(g);
+    s.bytes = cv.off;
     return s;
 }
 
@@ -68,17 +63,15 @@ struct Work {
 
 Work carve_work(void *base, int n, int k, int c, int g) {
     Work w;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += al(bytes); return r; };
+    PtvCarver cv{(char *)base, 0};
     w.dense_bytes = dense_workspace_bytes(n, 5 * c, c);  // five weight gradients in one launch
-    w.dense = take(w.dense_bytes);
+    w.dense = cv.take(w.dense_bytes);
     w.gva_bytes = gva_block_workspace_bytes(n, k, c, g);
-    w.gva = take(w.gva_bytes);
-    for (int i = 0; i < 7; ++i) w.t[i] = (float *)take(sizeof(float) * (size_t)n * c);
+    w.gva = cv.take(w.gva_bytes);
+    for (int i = 0; i < 7; ++i) w.t[i] = cv.take_n<float>((size_t)n * c);
     // (records of 16 rows: the deep levels' k-split GEMM and attention tile kernels leave them per 16-row block)
-    for (int i = 0; i < 4; ++i) w.stat[i] = (float *)take(sizeof(float) * bn_tiles_floats_rb(n, c, 16));
-    w.bytes = off;
+    for (int i = 0; i < 4; ++i) w.stat[i] = cv.take_n<float>(bn_tiles_floats_rb(n, c, 16));
+    w.bytes = cv.off;
     return w;
 }
 
@@ -140,12 +133,6 @@ void fill_gva(const ptv2_block *B, const Saved &S, ptv2_gva_block *V) {
 }
 
 }  // namespace
-
-#define RUN(call)                        \
-    do {                                 \
-        int rc_ = (call);                \
-        if (rc_ != PTV2_OK) return rc_;  \
-    } while (0)
 
 extern "C" size_t ptv2_block_saved_bytes(int n, int k, int c, int g) {
     if (n < 0 || k < 1 || c < 1 || g < 1) return 0;

@@ -560,16 +560,14 @@ __global__ __launch_bounds__(TPB) void distill_backward_kernel(int n, int K, con
 
 bool dims_ok(int K, int C) { return K >= 1 && K <= MAXK && C >= 4 && C <= MAXC && C % 4 == 0; }
 int chunks_of(int max_rows) { return max_rows > 0 ? divup(max_rows, CHUNK) : 1; }
-size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" size_t cac_workspace_bytes(int b, int max_rows, int n, int k, int c) {
     if (b < 1 || max_rows < 0 || n < 0 || !dims_ok(k, c)) return 0;
     const size_t slabs = (size_t)b * chunks_of(max_rows);
     const size_t wsum = sizeof(float) * slabs * ((size_t)k * c + k);
-    const size_t distill = sizeof(float) * ((size_t)divup(n > 0 ? n : 1, CHUNK) * 3 * k) + al(sizeof(float) * 3 * k);
-    return al(wsum > distill ? wsum : distill) + 256;
+    const size_t distill = sizeof(float) * ((size_t)divup(n > 0 ? n : 1, CHUNK) * 3 * k) + ptv2_align256(sizeof(float) * 3 * k);
+    return ptv2_align256(wsum > distill ? wsum : distill) + 256;
 }
 
 extern "C" int cac_weighted_sum_forward_hip_launcher(int mode, int n, int b, int max_rows, int k, int c, const float *x,
@@ -633,9 +631,9 @@ extern "C" int cac_distill_forward_hip_launcher(int n, int k, const float *pred,
     if (n < 1 || k < 1 || k > MAXK || !pred || !soft || !label || !loss || !coef) return PTV2_ERR_ARG;
     const int chunks = divup(n, CHUNK);
     const size_t part_bytes = sizeof(float) * (size_t)chunks * 3 * k;
-    if (!workspace || workspace_bytes < part_bytes + al(sizeof(float) * 3 * k)) return PTV2_ERR_WORKSPACE;
+    if (!workspace || workspace_bytes < part_bytes + ptv2_align256(sizeof(float) * 3 * k)) return PTV2_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    float *part = (float *)workspace, *sums = (float *)((char *)workspace + al(part_bytes));
+    float *part = (float *)workspace, *sums = (float *)((char *)workspace + ptv2_align256(part_bytes));
     hipLaunchKernelGGL(distill_partial_kernel, dim3(chunks), dim3(TPB), 0, st, n, k, pred, soft, label, part);
     hipLaunchKernelGGL(distill_class_kernel, dim3(k), dim3(64), 0, st, k, chunks, (const float *)part, sums);
     hipLaunchKernelGGL(distill_finalize_kernel, dim3(1), dim3(64), 0, st, k, (const float *)sums, loss, coef);

@@ -13,17 +13,33 @@
         if (hipGetLastError() != hipSuccess) return PTV2_ERR_LAUNCH; \
     } while (0)
 
+// inside a launcher: pass a failing status of a stage on
+#define RUN(call)                        \
+    do {                                 \
+        int rc_ = (call);                \
+        if (rc_ != PTV2_OK) return rc_;  \
+    } while (0)
+
 static inline int divup(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// Every region of a workspace / saved buffer / arena starts on a 256-byte boundary.
+static constexpr size_t ptv2_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// Carves consecutive aligned regions out of a caller-owned buffer; p == NULL only measures (off = bytes needed so far).
+struct PtvCarver {
+    char *p; size_t off;
+    char *take(size_t bytes) { char *r = p ? p + off : nullptr; off += ptv2_align256(bytes); return r; }
+    template <class T> T *take_n(size_t count) { return (T *)take(sizeof(T) * count); }
+};
 
 // The A/B switches of the library (environment variables; the parity tests flip them), all read through these two helpers.
 // A site that keeps the result in a `static const` reads once per process, any other site on every call -- part of the test
 // contract: the per-call ones are flipped with monkeypatch.setenv, tests/test_gpu_env_variants.py starts a child for the others.
 //   name                      unit                       read       meaning
-//   AO_AMD_BWD_STAGED         gva_aggregate.hip          per call   set: staged launches in every attention stage (gva_bwd_staged())
-//   AO_AMD_BWD_POINT          gva_aggregate.hip          per call   set: the point kernel instead of the backward tile kernel
-//   AO_AMD_FWD_STAGED         gva_block.hip              per call   set: the three staged forward launches (gva_fwd_staged())
-//   AO_AMD_TILE_KEEP_A        gva_block.hip              per call   set: the tile forward writes A (the A-reading weight gradient)
-//   AO_AMD_LOGITS_BWD         gva_bwd.hip                per call   "staged": the three-kernel logits backward (first letter s)
+//   AO_AMD_BWD_STAGED         gva_plan.hip: gva_plan()   per call   set: staged launches in every attention stage
+//   AO_AMD_BWD_POINT          gva_plan.hip: gva_plan()   per call   set: the point kernel instead of the backward tile kernel
+//   AO_AMD_FWD_STAGED         gva_plan.hip: gva_plan()   per call   set: the three staged forward launches
+//   AO_AMD_TILE_KEEP_A        gva_plan.hip: gva_plan()   per call   set: the tile forward writes A (the A-reading weight gradient)
+//   AO_AMD_LOGITS_BWD         gva_plan.hip: gva_plan()   per call   "staged": the three-kernel logits backward (first letter s)
 //   AO_AMD_BN_FINAPPLY        bn.hip                     per call   0: separate finalize + apply launches (bn_finapply_off())
 //   AO_AMD_GEMM               gemm.hip                   per call   "direct" | "lds": the older row GEMM forms (plain getenv: first letter d / l)
 //   AO_AMD_FPS_LOCAL          fps.hip                    per call   0: the device-scope exchange instead of one XCD per cloud

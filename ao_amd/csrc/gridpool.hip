@@ -19,8 +19,6 @@
 namespace {
 
 constexpr int TPB = 256;
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct PoolDims {
     long long nx, ny, nz;  // voxels per axis over the whole batch
     long long total;       // nx * ny * nz * clouds: must stay below 2^KEY_BITS
@@ -280,37 +278,28 @@ struct Ws {
 
 static Ws carve(void *base, int n, int b) {
     Ws w;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += al(bytes); return r; };
-    w.lo = (float *)take(sizeof(float) * 3 * b);
-    w.hi = (float *)take(sizeof(float) * 3 * b);
-    w.dims = (PoolDims *)take(sizeof(PoolDims));
-    w.keys_in = (unsigned long long *)take(sizeof(unsigned long long) * n);
-    w.keys_out = (unsigned long long *)take(sizeof(unsigned long long) * n);
-    w.vals_in = (int *)take(sizeof(int) * n);
-    w.flags = (int *)take(sizeof(int) * n);
-    w.rank = (int *)take(sizeof(int) * n);
+    PtvCarver cv{(char *)base, 0};
+    w.lo = cv.take_n<float>(3 * b); w.hi = cv.take_n<float>(3 * b);
+    w.dims = cv.take_n<PoolDims>(1);
+    w.keys_in = cv.take_n<unsigned long long>(n); w.keys_out = cv.take_n<unsigned long long>(n);
+    w.vals_in = cv.take_n<int>(n); w.flags = cv.take_n<int>(n); w.rank = cv.take_n<int>(n);
     w.mm_bytes = segment_minmax_hip_workspace_bytes(b);
-    w.mm = take(w.mm_bytes);
+    w.mm = cv.take(w.mm_bytes);
     size_t s1 = 0, s2 = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, s1, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                              (const int *)nullptr, (int *)nullptr, n, 0, 64, (hipStream_t)0);
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, s2, (const int *)nullptr, (int *)nullptr, n, (hipStream_t)0);
     w.cub_bytes = std::max(s1, s2) + 256;
-    w.cub = take(w.cub_bytes);
+    w.cub = cv.take(w.cub_bytes);
     // dense path: the grid size is data dependent, so the table is sized from n -- 64 cells per point (PT-v2 levels have 3-12:
     // a 0.06 m grid over a 120 k-point scan is 1.4 M cells), at most DENSE_CAP -- and a grid beyond it takes the sort path.
     // (Sized for the cap whatever n, the tables were 100 MB of every stream's retained workspace, also for a 2 k-point call.)
     w.d_cells = std::min<long long>(DENSE_CAP, std::max<long long>(64ll * n, 1 << 16));
     const size_t cells = (size_t)w.d_cells + DSCAN_TILE;
-    w.d_count = (int *)take(sizeof(int) * cells);
-    w.d_base = (int2 *)take(sizeof(int2) * cells);
-    w.d_tiles = (int2 *)take(sizeof(int2) * (cells / DSCAN_TILE + 1));
-    w.d_key = (int *)take(sizeof(int) * n);
-    w.d_slot = (int *)take(sizeof(int) * n);
-    w.d_over = (int *)take(sizeof(int) * 4);
-    w.bytes = off;
+    w.d_count = cv.take_n<int>(cells); w.d_base = cv.take_n<int2>(cells);
+    w.d_tiles = cv.take_n<int2>(cells / DSCAN_TILE + 1);
+    w.d_key = cv.take_n<int>(n); w.d_slot = cv.take_n<int>(n); w.d_over = cv.take_n<int>(4);
+    w.bytes = cv.off;
     return w;
 }
 

@@ -498,30 +498,34 @@ constexpr int BWD_TILE_BLOCKS = 256 * 16;
 
 using namespace gva;
 
-// 1 when the backward of this shape runs the tile kernel (AO_AMD_BWD_POINT: the point kernel behind a peb_bwd launch instead)
-// AO_AMD_BWD_STAGED (the A/B switch of the tests, read on every call): the staged launches instead of every fused form of the
-// attention -- here, in gva_bwd.hip, gva_block.hip and the MFMA / point forms of the logits forward (gva_fwd.hip)
-bool gva_bwd_staged() { return ptv2_env_set("AO_AMD_BWD_STAGED"); }
-int gva_bwd_tile_path(int k, int c, int g) {
-    return gva_bwd_tile_supported(k, c, g) && !gva_bwd_staged() && !ptv2_env_set("AO_AMD_BWD_POINT");
+// (sized for every form of the backward, whatever the switches say: the records of the tile kernel wherever it is instantiated)
+static size_t agg_part_bytes(const GvaPlan &P, int n, int c, int g) {
+    return ptv2_align256(sizeof(float) * std::max({(size_t)BWD_TILE_BLOCKS * 4 * c, (size_t)MAX_BLOCKS * 2 * g, gva_bwd_point_part_floats(c, g),
+                                                   P.bwd_tile_shape ? gva_bwd_tile_part_floats(n, c, g) : (size_t)0}));
 }
 
-static size_t agg_part_bytes(int n, int k, int c, int g) {
-    return align_up(sizeof(float) * std::max({(size_t)BWD_TILE_BLOCKS * 4 * c, (size_t)MAX_BLOCKS * 2 * g, gva_bwd_point_part_floats(c, g),
-                                              gva_bwd_tile_supported(k, c, g) ? gva_bwd_tile_part_floats(n, c, g) : (size_t)0}));
+static size_t agg_workspace_bytes(const GvaPlan &P, int n, int k, int c, int g) {
+    const size_t rows = (size_t)n * k;
+    const size_t part = agg_part_bytes(P, n, c, g);
+    return part + 3 * ptv2_align256(sizeof(float) * rows * g) + dense_workspace_bytes((int)std::min<size_t>(rows, 2147483647), g, g) + 1024;
 }
 
 extern "C" size_t gva_aggregate_workspace_bytes(int n, int k, int c, int g) {
     if (n < 0 || k < 1 || c < 1 || g < 1) return 0;
-    const size_t rows = (size_t)n * k;
-    const size_t part = agg_part_bytes(n, k, c, g);
-    return part + 3 * align_up(sizeof(float) * rows * g) + dense_workspace_bytes((int)std::min<size_t>(rows, 2147483647), g, g) + 1024;
+    return agg_workspace_bytes(gva_plan(n, k, c, g, false, true), n, k, c, g);
 }
 
 extern "C" int gva_aggregate_forward_hip_launcher(int n, int k, int c, int g, const float *W1, const float *sc,
                                                   const float *sh, const float *Ww2, const float *bw2, const float *v,
                                                   const float *a, const float *b, const float *coord, const int *idx,
                                                   float *out_v, float *A, float *sw, float *w, void *stream) {
+    return gva_aggregate_forward(gva_plan(n, k, c, g, ptv2_attn_drop_current().thresh != 0, true), n, k, c, g, W1, sc, sh, Ww2, bw2, v,
+                                 a, b, coord, idx, out_v, A, sw, w, stream);
+}
+
+int gva_aggregate_forward(const GvaPlan &P, int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
+                          const float *Ww2, const float *bw2, const float *v, const float *a, const float *b, const float *coord,
+                          const int *idx, float *out_v, float *A, float *sw, float *w, void *stream) {
     if (n < 0 || !pow2(k) || k > 64 || c < 1 || g < 1 || c % g != 0) return PTV2_ERR_ARG;
     if (n == 0) return PTV2_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -529,7 +533,7 @@ extern "C" int gva_aggregate_forward_hip_launcher(int n, int k, int c, int g, co
     const int nb_rows = (int)std::min<long long>((rows + TPB - 1) / TPB, MAX_BLOCKS * 4);
     {
         PtvScopedTimer t(KID_SOFTMAX_ROWS, st, 4.0 * ((double)rows * (2 * g + 1) + (double)n * g));
-        if (k <= 16 && (g == 12 || g == 24 || g == 48 || g == 64) && !gva_bwd_staged()) {  // g = 6: rows
+        if (P.softmax == GvaPlan::SM_POINT) {
             const int rc = gva_softmax_point_launch(n, k, g, W1, sc, sh, Ww2, bw2, idx, w, sw, st, ptv2_attn_drop_current());
             if (rc != PTV2_OK) return rc;
         } else {
@@ -560,27 +564,31 @@ extern "C" int gva_aggregate_forward_hip_launcher(int n, int k, int c, int g, co
     return PTV2_OK;
 }
 
-// Wp2 / bp2 != NULL: the backward of the grouped projection is done inside the point kernel (g_A, g_sw are not read)
-static int aggregate_backward_impl(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
+// Either g_A / g_sw are handed in (behind a peb_bwd launch), or -- for the forms the plan marks fused_peb, which do the backward
+// of the grouped projection themselves and never materialise g_A (N,G,C) / g_sw -- Wp2 / bp2 and the inverse table
+int gva_aggregate_backward(const GvaPlan &P, int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
                                    const float *Ww2, const float *bw2, const float *v, const float *a, const float *b,
                                    const float *coord, const int *idx, const float *w, const float *g_out, const float *g_A,
                                    const float *g_sw, const float *g_fused_Wp2, const float *g_fused_bp2, const int *inv_ptr,
                                    const int *inv_rows, float *gW1, float *gsc, float *gsh, float *gWw2, float *gbw2, float *gv,
                                    float *ga, float *gb, void *workspace, size_t workspace_bytes, void *stream) {
+    if (g_A ? !g_sw : (!P.fused_peb || !inv_ptr || !g_fused_Wp2 || !g_fused_bp2)) return PTV2_ERR_ARG;
+    const GvaPlan::BwdAgg form = g_A ? P.bwd_agg_given_gA : P.bwd_agg;
     if (n < 0 || !pow2(k) || k > 64 || c < 1 || g < 1 || c % g != 0 || !pow2(c / g) || c / g > 64) return PTV2_ERR_ARG;
-    if (!workspace || workspace_bytes < gva_aggregate_workspace_bytes(n, k, c, g)) return PTV2_ERR_WORKSPACE;
+    if (!workspace || workspace_bytes < agg_workspace_bytes(P, n, k, c, g)) return PTV2_ERR_WORKSPACE;
     if (n == 0) return PTV2_OK;
     hipStream_t st = (hipStream_t)stream;
     const long long rows = (long long)n * k;
-    const size_t part_bytes = agg_part_bytes(n, k, c, g);
-    const size_t rows_bytes = align_up(sizeof(float) * (size_t)rows * g);
+    const size_t part_bytes = agg_part_bytes(P, n, c, g);
+    const size_t rows_bytes = ptv2_align256(sizeof(float) * (size_t)rows * g);
     char *base = (char *)workspace;
     float *part = (float *)base;
-    if (inv_ptr && g_fused_Wp2 && g_fused_bp2 && gva_bwd_tile_path(k, c, g)) {
+    switch (form) {
+    case GvaPlan::B_TILE: {
         // the deep levels: one launch per tile of points (gva_bwd_tile.hip), g_A = g_out Wp2 formed per 16-channel chunk in LDS
         {
             // W1, idx, coord, g_out, v rows (unique once) in; gW1 out
-            PtvScopedTimer t(KID_BWD_TILE_K + (g == 12 ? 0 : g == 24 ? 1 : g == 48 ? 2 : 3), st,
+            PtvScopedTimer t(KID_BWD_TILE_K + P.g_slot - 1, st,  // (+ 0..3 for G = 12, 24, 48, 64)
                              4.0 * ((double)rows * (2 * g + 1) + (double)n * (3 + 2 * c)));
             const PtvDeferScope defer;  // its record sums ride on the gv launch below (which needs none of them)
             const int rc = gva_bwd_tile_launch(n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, g_fused_Wp2, g_fused_bp2, gW1,
@@ -594,11 +602,12 @@ static int aggregate_backward_impl(int n, int k, int c, int g, const float *W1, 
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
     }
-    if (inv_ptr && gva_bwd_point_supported(k, c, g) && !gva_bwd_staged()) {
+    case GvaPlan::B_POINT_LOCAL:
+    case GvaPlan::B_POINT: {
         // one fused MFMA launch (+ its finalize) instead of tile / rows / finalizes / the G x G weight-gradient GEMM
         {
             // W1, idx, coord, g_out, g_sw, v rows (unique once), g_A in; gW1 out
-            PtvScopedTimer t(KID_BWD_POINT + (g == 6 ? 0 : g == 12 ? 1 : g == 24 ? 2 : g == 48 ? 3 : 4), st, 4.0 * ((double)rows * (2 * g + 1) + (double)n * (3 + 2 * c + g) + (double)n * g * c));
+            PtvScopedTimer t(KID_BWD_POINT + P.g_slot, st, 4.0 * ((double)rows * (2 * g + 1) + (double)n * (3 + 2 * c + g) + (double)n * g * c));
             const PtvDeferScope defer;  // its record sums ride on the gv launch below (which needs none of them)
             const int rc = gva_bwd_point_launch(n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, g_A, g_sw, gW1, gsc,
                                                 gsh, gWw2, gbw2, ga, gb, part, part_bytes / sizeof(float), st, g_fused_Wp2,
@@ -612,15 +621,15 @@ static int aggregate_backward_impl(int n, int k, int c, int g, const float *W1, 
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
     }
-    if (ptv2_attn_drop_current().thresh) return PTV2_ERR_ARG;  // attention dropout: the fused point kernel only
+    case GvaPlan::B_STAGED: break;  // the launches below
+    }
+    if (ptv2_attn_drop_current().thresh) return PTV2_ERR_ARG;  // attention dropout: the fused kernels only
     float *gw = (float *)(base + part_bytes);
     float *gz = (float *)(base + part_bytes + rows_bytes);
     float *yb = (float *)(base + part_bytes + 2 * rows_bytes);
     void *dense_ws = base + part_bytes + 3 * rows_bytes;
     const size_t dense_bytes = workspace_bytes - (part_bytes + 3 * rows_bytes);
 
-    constexpr int dummy = 0;
-    (void)dummy;
     const size_t lds_tile = sizeof(float4) * (size_t)k +
                             sizeof(float) * ((size_t)k * G4of(g) + (((size_t)k * GPof(g) + 3) & ~(size_t)3) +
                                              (((size_t)64 * GPof(g) + 3) & ~(size_t)3)) + sizeof(int) * k;
@@ -660,20 +669,7 @@ static int aggregate_backward_impl(int n, int k, int c, int g, const float *W1, 
     return linear_wgrad_hip_launcher((int)rows, g, g, gz, yb, gWw2, gbw2, dense_ws, dense_bytes, stream);
 }
 
-// gva_aggregate_backward with the backward of the grouped projection (gva_peb_backward) folded into the point kernel:
-// for the instances gva_bwd_point_local() names, g_A (N,G,C) and g_sw are never materialised.  Internal to block runtime.
-int gva_aggregate_backward_fused_peb(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
-                                     const float *Ww2, const float *bw2, const float *v, const float *a, const float *b,
-                                     const float *coord, const int *idx, const float *w, const float *g_out, const float *Wp2,
-                                     const float *bp2, const int *inv_ptr, const int *inv_rows, float *gW1, float *gsc,
-                                     float *gsh, float *gWw2, float *gbw2, float *gv, float *ga, float *gb, void *workspace,
-                                     size_t workspace_bytes, void *stream) {
-    if (!inv_ptr || !(gva_bwd_point_local(k, c, g) || gva_bwd_tile_path(k, c, g)) || !Wp2 || !bp2) return PTV2_ERR_ARG;
-    return aggregate_backward_impl(n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, w, g_out, nullptr, nullptr, Wp2, bp2,
-                                   inv_ptr, inv_rows, gW1, gsc, gsh, gWw2, gbw2, gv, ga, gb, workspace, workspace_bytes, stream);
-}
-
-// the public form of the above: backward of gva_attention_forward_hip_launcher (the grouped projection's backward folded in)
+// backward of gva_attention_forward_hip_launcher: the grouped projection's backward folded in
 extern "C" int gva_attention_backward_hip_launcher(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
                                                    const float *Ww2, const float *bw2, const float *v, const float *a,
                                                    const float *b, const float *coord, const int *idx, const float *w,
@@ -681,9 +677,10 @@ extern "C" int gva_attention_backward_hip_launcher(int n, int k, int c, int g, c
                                                    const int *inv_rows, float *gW1, float *gsc, float *gsh, float *gWw2, float *gbw2,
                                                    float *gv, float *ga, float *gb, void *workspace, size_t workspace_bytes,
                                                    void *stream) {
-    if (!gva_bwd_tile_supported(k, c, g)) return PTV2_ERR_ARG;
-    return gva_aggregate_backward_fused_peb(n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, w, g_out, Wp2, bp2, inv_ptr, inv_rows,
-                                            gW1, gsc, gsh, gWw2, gbw2, gv, ga, gb, workspace, workspace_bytes, stream);
+    const GvaPlan P = gva_plan(n, k, c, g, ptv2_attn_drop_current().thresh != 0, inv_ptr != nullptr);
+    if (!P.bwd_tile_shape) return PTV2_ERR_ARG;
+    return gva_aggregate_backward(P, n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, w, g_out, nullptr, nullptr, Wp2, bp2,
+                                  inv_ptr, inv_rows, gW1, gsc, gsh, gWw2, gbw2, gv, ga, gb, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gva_aggregate_backward_hip_launcher(int n, int k, int c, int g, const float *W1, const float *sc,
@@ -695,6 +692,7 @@ extern "C" int gva_aggregate_backward_hip_launcher(int n, int k, int c, int g, c
                                                    float *gsh, float *gWw2, float *gbw2, float *gv, float *ga,
                                                    float *gb, void *workspace, size_t workspace_bytes, void *stream) {
     if (!g_A || !g_sw) return PTV2_ERR_ARG;
-    return aggregate_backward_impl(n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, w, g_out, g_A, g_sw, nullptr, nullptr,
-                                   inv_ptr, inv_rows, gW1, gsc, gsh, gWw2, gbw2, gv, ga, gb, workspace, workspace_bytes, stream);
+    return gva_aggregate_backward(gva_plan(n, k, c, g, ptv2_attn_drop_current().thresh != 0, inv_ptr != nullptr), n, k, c, g, W1, sc,
+                                  sh, Ww2, bw2, v, a, b, coord, idx, w, g_out, g_A, g_sw, nullptr, nullptr, inv_ptr, inv_rows, gW1,
+                                  gsc, gsh, gWw2, gbw2, gv, ga, gb, workspace, workspace_bytes, stream);
 }

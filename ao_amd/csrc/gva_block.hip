@@ -249,18 +249,9 @@ __global__ __launch_bounds__(TPB) void bp2_grad_kernel(int n, int c, int g, cons
     if (counter && last_block_arrives(counter)) finalize_columns(part, gridDim.x, c, MapVec<float>{gbp2});
 }
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace gva
 
 using namespace gva;
-
-// the deep levels' one-launch forward (gva_fwd_tile.hip) is the path of this shape; AO_AMD_FWD_STAGED: the three staged launches
-static bool gva_fwd_staged() { return ptv2_env_set("AO_AMD_FWD_STAGED"); }
-static bool gva_tile_path(int k, int c, int g) { return gva_fwd_tile_supported(k, c, g) && !gva_fwd_staged(); }
-// 1 when the forward of this shape writes A (n, g, c) for the backward (block.hip sizes the saved buffer with it): the
-// staged launches, the full-resolution point kernel, or the tile path with AO_AMD_TILE_KEEP_A (the A-reading weight gradient)
-int gva_block_keeps_A(int k, int c, int g) { return !gva_tile_path(k, c, g) || ptv2_env_set("AO_AMD_TILE_KEEP_A"); }
 
 namespace {
 struct BlockWs {  // carve the block workspace
@@ -271,58 +262,39 @@ struct BlockWs {  // carve the block workspace
     size_t bytes;
 };
 
-BlockWs carve(void *base, int n, int k, int c, int g) {
+BlockWs carve(const GvaPlan &P, void *base, int n, int k, int c, int g) {
     BlockWs w;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += al(bytes); return r; };
+    PtvCarver cv{(char *)base, 0};
     const size_t rows = (size_t)n * k;
     w.stage_bytes = std::max({gva_workspace_bytes(n, k, c, g), gva_aggregate_workspace_bytes(n, k, c, g),
                               dense_workspace_bytes(n, c, c), dense_workspace_bytes(n, 2 * g, c),
                               dense_workspace_bytes((int)std::min<size_t>(rows, 2147483647), g, g)});
-    w.stage = take(w.stage_bytes);
-    w.out_v = (float *)take(sizeof(float) * (size_t)n * c);
+    w.stage = cv.take(w.stage_bytes);
+    w.out_v = cv.take_n<float>((size_t)n * c);
     // (g_A (n,g,c) / g_sw only where a peb_bwd launch hands them to the aggregation backward: not at the full-resolution level's
     // point kernel nor on the deep levels' tile path, which form them on chip)
-    const bool fused_peb = (gva_bwd_point_local(k, c, g) && !gva_bwd_staged()) || gva_bwd_tile_path(k, c, g);
-    w.gA = fused_peb ? nullptr : (float *)take(sizeof(float) * (size_t)n * g * c);
-    w.g_sw = fused_peb ? nullptr : (float *)take(sizeof(float) * (size_t)n * g);
-    w.gW1 = (float *)take(sizeof(float) * rows * g);
-    w.gkW = (float *)take(sizeof(float) * (size_t)n * g);
-    w.gqW = (float *)take(sizeof(float) * (size_t)n * g);
-    w.ga1 = (float *)take(sizeof(float) * 3 * c);
-    w.gb1 = (float *)take(sizeof(float) * c);
-    w.ga2 = (float *)take(sizeof(float) * 3 * c);
-    w.gb2 = (float *)take(sizeof(float) * c);
-    w.gM = (float *)take(sizeof(float) * (size_t)c * g);
-    w.gcW = (float *)take(sizeof(float) * g);
-    w.gsc = (float *)take(sizeof(float) * g);
-    w.gsh = (float *)take(sizeof(float) * g);
-    w.gWw1_k = (float *)take(sizeof(float) * (size_t)g * c);
-    w.gWw1_q = (float *)take(sizeof(float) * (size_t)g * c);
-    w.part = (float *)take(sizeof(float) * (size_t)MAX_BLOCKS * c);
+    w.gA = P.fused_peb ? nullptr : cv.take_n<float>((size_t)n * g * c);
+    w.g_sw = P.fused_peb ? nullptr : cv.take_n<float>((size_t)n * g);
+    w.gW1 = cv.take_n<float>(rows * g);
+    w.gkW = cv.take_n<float>((size_t)n * g); w.gqW = cv.take_n<float>((size_t)n * g);
+    w.ga1 = cv.take_n<float>(3 * c); w.gb1 = cv.take_n<float>(c); w.ga2 = cv.take_n<float>(3 * c); w.gb2 = cv.take_n<float>(c);
+    w.gM = cv.take_n<float>((size_t)c * g); w.gcW = cv.take_n<float>(g); w.gsc = cv.take_n<float>(g); w.gsh = cv.take_n<float>(g);
+    w.gWw1_k = cv.take_n<float>((size_t)g * c); w.gWw1_q = cv.take_n<float>((size_t)g * c);
+    w.part = cv.take_n<float>((size_t)MAX_BLOCKS * c);
     w.wp2_bytes = dense_workspace_bytes(n, c, c);
-    w.wp2_part = take(w.wp2_bytes);
+    w.wp2_part = cv.take(w.wp2_bytes);
     w.kq_bytes = dense_workspace_bytes(n, 2 * g, c);
-    w.kq_part = take(w.kq_bytes);
-    w.T1 = (double *)take(sizeof(double) * g);
-    w.T2 = (double *)take(sizeof(double) * g);
-    w.gT1 = (double *)take(sizeof(double) * g);
-    w.gT2 = (double *)take(sizeof(double) * g);
-    w.bytes = off;
+    w.kq_part = cv.take(w.kq_bytes);
+    w.T1 = cv.take_n<double>(g); w.T2 = cv.take_n<double>(g); w.gT1 = cv.take_n<double>(g); w.gT2 = cv.take_n<double>(g);
+    w.bytes = cv.off;
     return w;
 }
 }  // namespace
 
-#define RUN(call)                  \
-    do {                           \
-        int rc_ = (call);          \
-        if (rc_ != PTV2_OK) return rc_; \
-    } while (0)
-
 extern "C" size_t gva_block_workspace_bytes(int n, int k, int c, int g) {
     if (n < 0 || k < 1 || c < 1 || g < 1) return 0;
-    return carve(nullptr, n, k, c, g).bytes + 1024;
+    // (the fields the carve reads depend on neither dropout nor the inverse table)
+    return carve(gva_plan(n, k, c, g, false, true), nullptr, n, k, c, g).bytes + 1024;
 }
 
 namespace {
@@ -333,7 +305,7 @@ thread_local float *g_fold_scratch = nullptr;
 thread_local std::vector<gva::FoldMBwdArgs> *g_fold_queue = nullptr;
 }  // namespace
 size_t ptv2_gva_fold_scratch_floats(int c, int g) {
-    return gva::al(sizeof(float) * ((size_t)c * g + g + 2 * (size_t)g * c + 8 * (size_t)c + 64)) / sizeof(float);
+    return ptv2_align256(sizeof(float) * ((size_t)c * g + g + 2 * (size_t)g * c + 8 * (size_t)c + 64)) / sizeof(float);
 }
 void ptv2_gva_set_fold_scratch(float *p) { g_fold_scratch = p; }
 int ptv2_gva_flush_folds(void *stream) {
@@ -402,7 +374,8 @@ int gva_block_forward_stats(const ptv2_gva_block *B, float *out_stats, int *stat
     if (B->attn_drop_p < 0.f || B->attn_drop_p > 1.f) return PTV2_ERR_ARG;
     const gva::PtvAttnDropScope attn_drop(B->training ? B->attn_drop_p : 0.f, B->attn_drop_seed);
     if (n == 0) return PTV2_OK;
-    BlockWs W = carve(workspace, n, k, c, g);
+    const GvaPlan P = gva_plan(n, k, c, g, gva::ptv2_attn_drop_current().thresh != 0, true);
+    BlockWs W = carve(P, workspace, n, k, c, g);
     if (!workspace || workspace_bytes < W.bytes) return PTV2_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const double rows = (double)n * k;
@@ -417,25 +390,27 @@ int gva_block_forward_stats(const ptv2_gva_block *B, float *out_stats, int *stat
         RUN(skinny_linear_forward_pair(n, c, g, xs, B->Ww1, xsc, xsh, ys, stream));
     }
     // logits + their BatchNorm statistics; the final reduction of the sums also folds BN_w into (sc, sh)
-    RUN(gva_logits_forward_fold(n, k, c, g, B->kW, B->qW, B->a, B->b, B->M, B->cW, B->coord, B->idx, B->W1, W.T1, W.T2,
+    RUN(gva_logits_forward_fold(P, n, k, c, g, B->kW, B->qW, B->a, B->b, B->M, B->cW, B->coord, B->idx, B->W1, W.T1, W.T2,
                                 FoldWFwdArgs{B->gamma_w, B->beta_w, B->run_mean_w, B->run_var_w, B->batches_w, B->training, rows,
                                              B->eps_w, B->momentum_w, B->sc, B->sh, B->mean_w, B->rstd_w},
                                 W.stage, W.stage_bytes, stream));
-    // softmax, aggregation and the grouped projection: one launch at the full-resolution level (gva_fwd_point.hip), else three
-    if (gva_fwd_point_supported(k, c, g) && n <= gva_fwd_point_max_n() && !gva::ptv2_attn_drop_current().thresh &&
-        !gva_fwd_staged()) {
+    // softmax, aggregation and the grouped projection
+    switch (P.fwd) {
+    case GvaPlan::F_POINT:  // one launch at the full-resolution level (gva_fwd_point.hip)
         RUN(gva_fwd_point_launch(n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, B->Wp2, B->bp2,
                                  B->w, B->sw, B->A, B->out, out_stats, stream));
         if (out_stats && stats_done) *stats_done = 64;
-    } else if (gva_tile_path(k, c, g)) {
-        // the deep levels: one launch per 16-point tile x group block (gva_fwd_tile.hip); no out_v, no A
+        break;
+    case GvaPlan::F_TILE:  // the deep levels: one launch per 16-point tile x group block (gva_fwd_tile.hip); no out_v, no A
         RUN(gva_fwd_tile_launch(n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, B->Wp2, B->bp2,
-                                B->w, B->sw, B->out, out_stats, gva_block_keeps_A(k, c, g) ? B->A : nullptr, stream));
+                                B->w, B->sw, B->out, out_stats, P.keeps_A ? B->A : nullptr, stream));
         if (out_stats && stats_done) *stats_done = 16;
-    } else {
-        RUN(gva_aggregate_forward_hip_launcher(n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord,
-                                               B->idx, W.out_v, B->A, B->sw, B->w, stream));
+        break;
+    case GvaPlan::F_STAGED:  // three launches
+        RUN(gva_aggregate_forward(P, n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, W.out_v,
+                                  B->A, B->sw, B->w, stream));
         RUN(gva_peb_forward_stats(n, c, g, B->A, B->Wp2, B->bp2, B->sw, W.out_v, B->out, out_stats, stats_done, stream));
+        break;
     }
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
@@ -448,7 +423,8 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
     if (n < 0 || k < 1 || c < 4 || g < 1 || c % g != 0) return PTV2_ERR_ARG;
     if (n == 0) return PTV2_OK;
     const gva::PtvAttnDropScope attn_drop(B->training ? B->attn_drop_p : 0.f, B->attn_drop_seed);
-    BlockWs W = carve(workspace, n, k, c, g);
+    const GvaPlan P = gva_plan(n, k, c, g, gva::ptv2_attn_drop_current().thresh != 0, G->inv_ptr != nullptr);
+    BlockWs W = carve(P, workspace, n, k, c, g);
     if (!workspace || workspace_bytes < W.bytes) return PTV2_ERR_WORKSPACE;
     if (g_fold_scratch) {  // the glue's operands in the caller's per-Block region: they outlive this call
         float *p = g_fold_scratch;
@@ -474,9 +450,8 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
     PtvRiderGuard riders;  // an error return below must not leave queued sums (pointers into this call's workspace) behind
     // 1. projection after the neighbour sum: g_A, g_sw (formed inside the point kernel for the narrow instances),
     //    grad Wp2 (direct part), grad bp2 (direct part)
-    const bool fused_peb = (gva_bwd_point_local(k, c, g) && !gva_bwd_staged()) || gva_bwd_tile_path(k, c, g);
-    if (fused_peb && !G->inv_ptr) return PTV2_ERR_ARG;  // (the fused forms gather grad v through the inverse neighbour table)
-    if (!fused_peb) RUN(gva_peb_backward_hip_launcher(n, c, g, G->g_out, B->Wp2, B->bp2, W.gA, W.g_sw, stream));
+    if (P.fused_peb && !G->inv_ptr) return PTV2_ERR_ARG;  // (the fused forms gather grad v through the inverse neighbour table)
+    if (!P.fused_peb) RUN(gva_peb_backward_hip_launcher(n, c, g, G->g_out, B->Wp2, B->bp2, W.gA, W.g_sw, stream));
     int bp2_done = 0;
     {
         // the sum of its split-K records (needed by fold_m_bwd only) rides on the gv launch of the aggregation stage: records
@@ -484,7 +459,7 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
         // grad bp2 = sum_n g_out[n, ch] sw[n, group(ch)] as its weighted bias sums (it reads g_out anyway; that sum was a launch
         // of its own per Block, bp2_grad_kernel: 15 x 6 us); where the weight gradient cannot (bf16 operands), the kernel below
         const PtvDeferScope defer;
-        if (!gva_block_keeps_A(k, c, g)) {  // A = w^T P is formed again inside the weight gradient (gva_wgrad_tile.hip)
+        if (P.wp2_recompute) {  // A = w^T P is formed again inside the weight gradient (gva_wgrad_tile.hip)
             RUN(gva_wp2_wgrad_recompute(n, k, c, g, G->g_out, B->w, B->sw, B->a, B->b, B->coord, B->idx, G->gWp2, G->gbp2, W.wp2_part,
                                         W.wp2_bytes, stream));
             bp2_done = 1;
@@ -504,20 +479,16 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
         if (!own_final) launch_finalize(st, (const float *)W.part, nblk, c, MapVec<float>{G->gbp2});
     }
     // 2. softmax / aggregation stage
-    if (fused_peb)
-        RUN(gva_aggregate_backward_fused_peb(n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx,
-                                             B->w, G->g_out, B->Wp2, B->bp2, G->inv_ptr, G->inv_rows, W.gW1, W.gsc, W.gsh,
-                                             G->gWw2, G->gbw2, G->gv, W.ga2, W.gb2, W.stage, W.stage_bytes, stream));
-    else
-        RUN(gva_aggregate_backward_hip_launcher(n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord,
-                                                B->idx, B->w, G->g_out, W.gA, W.g_sw, G->inv_ptr, G->inv_rows, W.gW1, W.gsc,
-                                                W.gsh, G->gWw2, G->gbw2, G->gv, W.ga2, W.gb2, W.stage, W.stage_bytes, stream));
+    // (W.gA / W.g_sw are NULL exactly when the plan says fused_peb: the form then works from Wp2 / bp2)
+    RUN(gva_aggregate_backward(P, n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, B->w, G->g_out,
+                               W.gA, W.g_sw, P.fused_peb ? B->Wp2 : nullptr, P.fused_peb ? B->bp2 : nullptr, G->inv_ptr, G->inv_rows,
+                               W.gW1, W.gsc, W.gsh, G->gWw2, G->gbw2, G->gv, W.ga2, W.gb2, W.stage, W.stage_bytes, stream));
     // 3. + 4. BatchNorm over the logits (its backward is evaluated in the prologue of the rows kernel), logits stage
     if (!G->inv_ptr) (void)ptv2_zero_async(W.gkW, sizeof(float) * (size_t)n * g, st);
     // the parameter-gradient sums of this stage and of the kW / qW weight gradient ride on the skinny_bwd launch below
     {
     const PtvDeferScope defer;
-    RUN(gva_logits_backward_foldw(n, k, c, g, B->a, B->b, B->M, B->coord, B->idx, B->W1, W.gW1, nullptr, nullptr,
+    RUN(gva_logits_backward_foldw(P, n, k, c, g, B->a, B->b, B->M, B->coord, B->idx, B->W1, W.gW1, nullptr, nullptr,
                                   FoldWBwdArgs{B->gamma_w, B->mean_w, B->rstd_w, B->training, rows, W.gsc, W.gsh, G->ggamma_w,
                                                G->gbeta_w},
                                   G->inv_ptr, G->inv_rows, W.gkW, W.gqW, W.ga1, W.gb1, W.gM, W.gcW, W.stage, W.stage_bytes, stream));

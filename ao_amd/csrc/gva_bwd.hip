@@ -258,11 +258,13 @@ extern "C" int gva_logits_backward_hip_launcher(int n, int k, int c, int g, cons
                                                 const double *gT2, const int *inv_ptr, const int *inv_rows,
                                                 float *gkW, float *gqW, float *ga, float *gb, float *gM, float *gcW,
                                                 void *workspace, size_t workspace_bytes, void *stream) {
-    return gva_logits_backward_foldw(n, k, c, g, a, b, M, coord, idx, W1, gW1, gT1, gT2, gva::FoldWBwdArgs{}, inv_ptr, inv_rows, gkW,
+    return gva_logits_backward_foldw(gva_plan(n, k, c, g, false, inv_ptr != nullptr), n, k, c, g, a, b, M, coord, idx, W1, gW1, gT1,
+                                     gT2, gva::FoldWBwdArgs{}, inv_ptr, inv_rows, gkW,
                                      gqW, ga, gb, gM, gcW, workspace, workspace_bytes, stream);
 }
 
-int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
+int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, const float *a, const float *b, const float *M,
+                              const float *coord,
                               const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
                               const gva::FoldWBwdArgs &F, const int *inv_ptr, const int *inv_rows, float *gkW, float *gqW, float *ga,
                               float *gb, float *gM, float *gcW, void *workspace, size_t workspace_bytes, void *stream) {
@@ -274,11 +276,10 @@ int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const 
     float *part = (float *)workspace;
     float *gWt = (float *)((char *)workspace + rows_offset_bytes(c, g));
     // wide-group levels: rows + parameter gradients in one pipelined MFMA launch (gva_bwd_logits.hip), then the gather
-    const bool fused_off = ptv2_env_is("AO_AMD_LOGITS_BWD", 's');  // "staged": the three-kernel form (A/B switch of the tests)
-    if (inv_ptr && gva_logits_bwd_fused_supported(k, c, g) && !fused_off && !gva_bwd_staged()) {
+    if (P.logits_bwd == GvaPlan::LB_FUSED) {
         {
             // W1, gW1 in, gWt out, idx, coord; parameter-sized outputs
-            PtvScopedTimer t(KID_LOGITS_BWD_FUSED + (g == 6 ? 0 : g == 12 ? 1 : g == 24 ? 2 : g == 48 ? 3 : 4), st,
+            PtvScopedTimer t(KID_LOGITS_BWD_FUSED + P.g_slot, st,
                              4.0 * ((double)rows * (3 * g + 1) + 3.0 * n));
             const int rc = gva_logits_bwd_fused_launch(n, k, c, g, a, b, M, coord, idx, W1, gW1, gT1, gT2, F, gWt, part,
                                                        part_floats(c, g), gM, ga, gb, gcW, st);
@@ -312,7 +313,7 @@ int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const 
     const size_t comb_bytes = sizeof(float) * (size_t)nsl * cbk * (g + 4);
     // enough workgroups to hide the tile-load latency (8 per CU), bounded by the partial-sum budget
     const int par_cap = (int)std::max<long long>(64, std::min<long long>(MAX_BLOCKS, ((long long)MAX_PARAM_BLOCKS * 24576) / ((long long)c * (g + 4))));
-    if (g >= 48 && gva_bwd_point_supported(k, c, g) && !gva_bwd_staged()) {  // pays for wide G only
+    if (P.logits_bwd == GvaPlan::LB_ROWS_POINT_PARAMS) {
         int nb = 0;
         {
             PtvScopedTimer t(KID_LOGITS_BWD_PARAMS, st, 4.0 * ((double)rows * (g + 1) + 3.0 * n));

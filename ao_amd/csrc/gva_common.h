@@ -3,13 +3,12 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gva_plan.h"
 
 namespace gva {
 
 constexpr int TPB = 256;
 constexpr int WPB = TPB / WAVE;  // waves per block
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 constexpr int MAX_BLOCKS = 256 * 8;   // grid cap of the row-parallel stages
 constexpr int MAX_PARAM_BLOCKS = 256;
@@ -24,7 +23,7 @@ inline size_t part_floats(int c, int g) {
     m = m > agg_bwd ? m : agg_bwd;
     return m < 9 * (size_t)MAX_BLOCKS ? 9 * (size_t)MAX_BLOCKS : m;
 }
-inline size_t rows_offset_bytes(int c, int g) { return align_up(sizeof(float) * part_floats(c, g)); }
+inline size_t rows_offset_bytes(int c, int g) { return ptv2_align256(sizeof(float) * part_floats(c, g)); }
 
 // masked relative position of neighbour slot (n, s)
 struct Rel {

@@ -213,7 +213,7 @@ using namespace gva;
 extern "C" size_t gva_workspace_bytes(int n, int k, int c, int g) {
     if (n < 0 || k < 1 || c < 1 || g < 1) return 0;
     // [per-block partial sums of the widest stage][one (n,k,g) fp32 row buffer: gWt / w]
-    return rows_offset_bytes(c, g) + align_up(sizeof(float) * (size_t)n * k * g) + 1024;
+    return rows_offset_bytes(c, g) + ptv2_align256(sizeof(float) * (size_t)n * k * g) + 1024;
 }
 
 extern "C" int gva_pos_stats_hip_launcher(int n, int k, const float *coord, const int *idx, double *s1, double *s2,
@@ -277,7 +277,8 @@ extern "C" int gva_pos_moments_hip_launcher(int n, int k, const float *coord, co
 }
 
 // F.sc != NULL: the final reduction also folds BN_w (block runtime); the C entry point below passes none
-int gva_logits_forward_fold(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
+int gva_logits_forward_fold(const GvaPlan &P, int n, int k, int c, int g, const float *kW, const float *qW, const float *a,
+                            const float *b,
                             const float *M, const float *cW, const float *coord, const int *idx, float *W1, double *T1, double *T2,
                             const gva::FoldWFwdArgs &F, void *workspace, size_t workspace_bytes, void *stream) {
     if (n < 0 || k < 1 || c < 1 || g < 1) return PTV2_ERR_ARG;
@@ -285,18 +286,11 @@ int gva_logits_forward_fold(int n, int k, int c, int g, const float *kW, const f
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace;
     const long long rows = (long long)n * k;
-    {
-        if (gva_logits_fwd_mfma_supported(k, c, g) && !gva_bwd_staged()) {
-            PtvScopedTimer t(KID_LOGITS_FWD, st, 4.0 * ((double)n * k * (g + 1) + (double)n * (3 + 2 * g)));
-            const int rc = gva_logits_fwd_mfma_launch(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st);
-            if (rc != PTV2_OK) return rc;
-            PTV2_CHECK_LAUNCH();
-            return PTV2_OK;
-        }
-    }
-    if (k <= 16 && c % 4 == 0 && (g == 48 || g == 64) && !gva_bwd_staged()) {  // pays for wide G only
+    if (P.logits_fwd != GvaPlan::LF_ROWS) {
         PtvScopedTimer t(KID_LOGITS_FWD, st, 4.0 * ((double)n * k * (g + 1) + (double)n * (3 + 2 * g)));
-        const int rc = gva_logits_point_launch(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st);
+        const int rc = P.logits_fwd == GvaPlan::LF_MFMA
+                           ? gva_logits_fwd_mfma_launch(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st)
+                           : gva_logits_point_launch(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st);
         if (rc != PTV2_OK) return rc;
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
@@ -341,6 +335,7 @@ extern "C" int gva_logits_forward_hip_launcher(int n, int k, int c, int g, const
                                                const float *a, const float *b, const float *M, const float *cW,
                                                const float *coord, const int *idx, float *W1, double *T1, double *T2,
                                                void *workspace, size_t workspace_bytes, void *stream) {
-    return gva_logits_forward_fold(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, T1, T2, gva::FoldWFwdArgs{}, workspace,
+    return gva_logits_forward_fold(gva_plan(n, k, c, g, false, true), n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, T1, T2,
+                                   gva::FoldWFwdArgs{}, workspace,
                                    workspace_bytes, stream);
 }

@@ -5,6 +5,7 @@
 // which the callers include, define them.  (common.h and gva_common.h keep the interfaces that sit next to their types.)
 #pragma once
 
+struct GvaPlan;  // gva_plan.h
 namespace gva { struct FoldWFwdArgs; struct FoldWBwdArgs; struct PtvDrop; }
 namespace dense { struct WgradJob; }
 
@@ -57,7 +58,6 @@ int gva_wp2_wgrad_recompute(int n, int k, int c, int g, const float *g_out, cons
 // ---- block.hip --------------------------------------------------------------------------------------------------------
 int ptv2_blocks_fold_forward(int count, const ptv2_block *blocks, void *stream);
 // ---- gva_block.hip ----------------------------------------------------------------------------------------------------
-int gva_block_keeps_A(int k, int c, int g);
 int gva_fold_forward_batched(int count, const ptv2_gva_block *blocks, void *stream);
 int gva_block_forward_stats(const ptv2_gva_block *B, float *out_stats, int *stats_done, void *workspace, size_t workspace_bytes,
                             void *stream);
@@ -67,7 +67,7 @@ void ptv2_gva_set_fold_scratch(float *p);
 int ptv2_gva_flush_folds(void *stream);
 void ptv2_gva_drop_folds();
 // ---- gva_fwd.hip ------------------------------------------------------------------------------------------------------
-int gva_logits_forward_fold(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
+int gva_logits_forward_fold(const GvaPlan &P, int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
                             const float *M, const float *cW, const float *coord, const int *idx, float *W1, double *T1, double *T2,
                             const gva::FoldWFwdArgs &F, void *workspace, size_t workspace_bytes, void *stream);
 // ---- gva_fwd_point.hip ------------------------------------------------------------------------------------------------
@@ -86,18 +86,21 @@ int gva_fwd_tile_launch(int n, int k, int c, int g, const float *W1, const float
 int gva_peb_forward_stats(int n, int c, int g, const float *A, const float *Wp2, const float *bp2, const float *sw,
                           const float *out_v, float *out, float *stats, int *stats_done, void *stream);
 // ---- gva_aggregate.hip ------------------------------------------------------------------------------------------------
-bool gva_bwd_staged();  // AO_AMD_BWD_STAGED is set: the staged launches in every stage of the attention
-int gva_bwd_tile_path(int k, int c, int g);
-int gva_aggregate_backward_fused_peb(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
-                                     const float *Ww2, const float *bw2, const float *v, const float *a, const float *b,
-                                     const float *coord, const int *idx, const float *w, const float *g_out, const float *Wp2,
-                                     const float *bp2, const int *inv_ptr, const int *inv_rows, float *gW1, float *gsc, float *gsh,
-                                     float *gWw2, float *gbw2, float *gv, float *ga, float *gb, void *workspace,
-                                     size_t workspace_bytes, void *stream);
+// the public stage launchers behind a plan the caller has made already (gva_block.hip)
+int gva_aggregate_forward(const GvaPlan &P, int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
+                          const float *Ww2, const float *bw2, const float *v, const float *a, const float *b, const float *coord,
+                          const int *idx, float *out_v, float *A, float *sw, float *w, void *stream);
+// g_A / g_sw, or NULL for both and Wp2 / bp2 where the plan says fused_peb
+int gva_aggregate_backward(const GvaPlan &P, int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
+                           const float *Ww2, const float *bw2, const float *v, const float *a, const float *b, const float *coord,
+                           const int *idx, const float *w, const float *g_out, const float *g_A, const float *g_sw, const float *Wp2,
+                           const float *bp2, const int *inv_ptr, const int *inv_rows, float *gW1, float *gsc, float *gsh,
+                           float *gWw2, float *gbw2, float *gv, float *ga, float *gb, void *workspace, size_t workspace_bytes,
+                           void *stream);
 // ---- gva_bwd.hip ------------------------------------------------------------------------------------------------------
 // F.gsc != NULL: gT1 / gT2 are not read; the rows kernel derives them from the fold_w backward (and writes the BatchNorm's
 // parameter gradients)
-int gva_logits_backward_foldw(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
+int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
                               const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
                               const gva::FoldWBwdArgs &F, const int *inv_ptr, const int *inv_rows, float *gkW, float *gqW,
                               float *ga, float *gb, float *gM, float *gcW, void *workspace, size_t workspace_bytes, void *stream);
@@ -113,7 +116,7 @@ int gva_logits_fwd_mfma_launch(int n, int k, int c, int g, const float *kW, cons
                                double *T1, double *T2, const gva::FoldWFwdArgs &F, hipStream_t st);
 // ---- gva_bwd_point.hip: the fused MFMA backward (one launch) for the (k, c, g) it is instantiated for -----------------
 int gva_bwd_point_supported(int k, int c, int g);
-int gva_bwd_point_local(int k, int c, int g);
+int gva_bwd_point_local(int k, int c, int g);  // the instances that can form g_A / g_sw themselves (shape only; gva_plan() decides)
 size_t gva_bwd_point_part_floats(int c, int g);
 int gva_bwd_point_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
                          const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,

@@ -36,8 +36,6 @@ constexpr int MIN_WIDTH = 256, MAX_WIDTH = 4096;  // keys per partition (a power
 constexpr int STAGE = 12288;                // members a partition stages in LDS (48 KB); larger ones go through global scratch
 constexpr int SCAN_TPB = 1024, SCAN_ITEMS = 4, SCAN_TILE = SCAN_TPB * SCAN_ITEMS;
 constexpr int GROUP = 16, GROUPS = TPB / GROUP;
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct InvJobs {
     int count;
     int n[INV_MAX];             // points of job t (keys 0 .. n: key 0 = the -1 placeholders)
@@ -284,10 +282,10 @@ int make_plan(int count, const ptv2_inverse_job *jobs, Plan &P) {
     P.cells_used = (int)cells;
     P.scan_wgs = (int)((cells + SCAN_TILE - 1) / SCAN_TILE);
     P.cells_padded = P.scan_wgs * SCAN_TILE;
-    P.cell_bytes = al(sizeof(int) * (size_t)P.cells_padded);
-    P.handoff_bytes = al(sizeof(unsigned long long) * (size_t)P.scan_wgs);
-    P.pair_bytes = al(sizeof(int2) * (size_t)rows);
-    P.spill_bytes = al(sizeof(int) * (size_t)rows);
+    P.cell_bytes = ptv2_align256(sizeof(int) * (size_t)P.cells_padded);
+    P.handoff_bytes = ptv2_align256(sizeof(unsigned long long) * (size_t)P.scan_wgs);
+    P.pair_bytes = ptv2_align256(sizeof(int2) * (size_t)rows);
+    P.spill_bytes = ptv2_align256(sizeof(int) * (size_t)rows);
     return PTV2_OK;
 }
 

@@ -54,27 +54,20 @@ constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_TILE = SCAN_ITEMS * SCAN_THREADS;
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 Workspace carve(void *base, int m, int n, int b) {
     Workspace w;
     size_t ncell = (size_t)CELLS_PER_POINT * n + b + 1;
     size_t ncell_pad = (size_t)divup(ncell + 1, SCAN_TILE) * SCAN_TILE;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-    w.tie_count = (int *)take(sizeof(int) * 4);
-    w.bbox_lo = (int *)take(sizeof(int) * 3 * b);
-    w.bbox_hi = (int *)take(sizeof(int) * 3 * b);
-    w.seg = (SegGrid *)take(sizeof(SegGrid) * b);
-    w.block_sums = (int *)take(sizeof(int) * (ncell_pad / SCAN_TILE + 1));
-    w.cell_count = (int *)take(sizeof(int) * ncell_pad);
-    w.cell_start = (int *)take(sizeof(int) * (ncell_pad + 1));
-    w.point_cell = (int *)take(sizeof(int) * n);
-    w.point_rank = (int *)take(sizeof(int) * n);
-    w.sorted = (float4 *)take(sizeof(float4) * n);
-    w.tie_list = (int *)take(sizeof(int) * (m > 0 ? m : 1));
-    w.bytes = off;
+    PtvCarver cv{(char *)base, 0};
+    w.tie_count = cv.take_n<int>(4);
+    w.bbox_lo = cv.take_n<int>(3 * b); w.bbox_hi = cv.take_n<int>(3 * b);
+    w.seg = cv.take_n<SegGrid>(b);
+    w.block_sums = cv.take_n<int>(ncell_pad / SCAN_TILE + 1);
+    w.cell_count = cv.take_n<int>(ncell_pad); w.cell_start = cv.take_n<int>(ncell_pad + 1);
+    w.point_cell = cv.take_n<int>(n); w.point_rank = cv.take_n<int>(n);
+    w.sorted = cv.take_n<float4>(n);
+    w.tie_list = cv.take_n<int>(m > 0 ? m : 1);
+    w.bytes = cv.off;
     return w;
 }
 

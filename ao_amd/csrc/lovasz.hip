@@ -46,20 +46,18 @@ constexpr int LV_MAX_C = 1024;
 constexpr unsigned LV_ONE = 0x3F800000u;
 enum { M_NSEG = 0, M_NLAB = 1, M_BAD = 2, M_WORDS = 16 };
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct SavedLayout {  // per call, kept for the backward
     size_t meta, cls_cnt, slot_of, cls_of_slot, rank_of, rowstat, gs, total;
     SavedLayout(int n, int c) {
         const size_t segs = (size_t)std::min(n, c);
         meta = 0;
         cls_cnt = meta + sizeof(int) * M_WORDS;
-        slot_of = al(cls_cnt + sizeof(int) * c);
-        cls_of_slot = slot_of + al(sizeof(int) * c);
-        rank_of = cls_of_slot + al(sizeof(int) * c);
-        rowstat = rank_of + al(sizeof(int) * n);
-        gs = rowstat + al(sizeof(float) * 2 * n);
-        total = gs + al(sizeof(float) * segs * n);
+        slot_of = ptv2_align256(cls_cnt + sizeof(int) * c);
+        cls_of_slot = slot_of + ptv2_align256(sizeof(int) * c);
+        rank_of = cls_of_slot + ptv2_align256(sizeof(int) * c);
+        rowstat = rank_of + ptv2_align256(sizeof(int) * n);
+        gs = rowstat + ptv2_align256(sizeof(float) * 2 * n);
+        total = gs + ptv2_align256(sizeof(float) * segs * n);
     }
 };
 
@@ -71,14 +69,14 @@ struct WsLayout {  // scratch of one forward call
         const int nblk = (n + LV_ROWS - 1) / LV_ROWS;
         cps = (n + LV_CHUNK - 1) / LV_CHUNK;
         blkcnt = 0;
-        keys0 = al(sizeof(int) * nblk);
-        vals0 = keys0 + al(4 * elems);
-        keys1 = vals0 + al(4 * elems);
-        vals1 = keys1 + al(4 * elems);
-        cnt = vals1 + al(4 * elems);
-        chunkfg = cnt + al(sizeof(int) * segs * 256 * cps);
-        part = chunkfg + al(sizeof(int) * segs * cps);
-        total = part + al(sizeof(double) * segs * cps);
+        keys0 = ptv2_align256(sizeof(int) * nblk);
+        vals0 = keys0 + ptv2_align256(4 * elems);
+        keys1 = vals0 + ptv2_align256(4 * elems);
+        vals1 = keys1 + ptv2_align256(4 * elems);
+        cnt = vals1 + ptv2_align256(4 * elems);
+        chunkfg = cnt + ptv2_align256(sizeof(int) * segs * 256 * cps);
+        part = chunkfg + ptv2_align256(sizeof(int) * segs * cps);
+        total = part + ptv2_align256(sizeof(double) * segs * cps);
     }
 };
 

@@ -28,8 +28,6 @@ namespace {
 
 constexpr int TPB = 256;
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // y[r, o] = sum_i x[r, i] W[o, i] + b[o] for a narrow side (cin or cout not a multiple of 4, or tiny): the patch embedding's
 // Linear(in_channels = 6 or 9, c0) and the classifier Linear(c0, num_classes = 13 or 20).  One thread per output element,
 // W and b in LDS; the x row of a thread is shared with its cout neighbours through L1.
@@ -211,49 +209,39 @@ bool prefix_ok(const ptv2_model *M) {
 Arena carve(const ptv2_model *M, void *base, void *base0 = nullptr, bool split = false, bool prefix_only = false) {
     Arena A{};
     split = split || base0 != nullptr;
-    char *p = (char *)base, *p0 = (char *)base0;
-    size_t off = 0, off0 = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += al(bytes); return r; };
-    auto take0 = [&](size_t bytes) {
-        if (!split) return take(bytes);
-        char *r = p0 ? p0 + off0 : nullptr;
-        off0 += al(bytes);
-        return r;
-    };
+    PtvCarver cv{(char *)base, 0}, prefix{(char *)base0, 0};
+    PtvCarver &cv0 = split ? prefix : cv;  // the prefix's items: from their own region when there is one
     auto linbn = [&](const ptv2_linbn &L, int n, bool keep_y) {
         LinBnSaved s;
-        s.h = (float *)take(sizeof(float) * (size_t)n * L.cout);
-        s.y = keep_y ? (float *)take(sizeof(float) * (size_t)n * L.cout) : nullptr;
-        s.mean = (float *)take(sizeof(float) * L.cout);
-        s.rstd = (float *)take(sizeof(float) * L.cout);
+        s.h = cv.take_n<float>((size_t)n * L.cout);
+        s.y = keep_y ? cv.take_n<float>((size_t)n * L.cout) : nullptr;
+        s.mean = cv.take_n<float>(L.cout); s.rstd = cv.take_n<float>(L.cout);
         return s;
     };
     const int S = M->num_stages;
     {   // the prefix first
         const ptv2_linbn &L = M->embed;
         const int n = M->level[0].n;
-        A.embed.h = (float *)take0(sizeof(float) * (size_t)n * L.cout);
-        A.embed.y = (float *)take0(sizeof(float) * (size_t)n * L.cout);
-        A.embed.mean = (float *)take0(sizeof(float) * L.cout);
-        A.embed.rstd = (float *)take0(sizeof(float) * L.cout);
+        A.embed.h = cv0.take_n<float>((size_t)n * L.cout); A.embed.y = cv0.take_n<float>((size_t)n * L.cout);
+        A.embed.mean = cv0.take_n<float>(L.cout); A.embed.rstd = cv0.take_n<float>(L.cout);
         const ptv2_seq &s = M->seq[0];
         if (!M->checkpoint)
             for (int j = 0; j < s.depth; ++j) {
                 const int b = s.first_block + j;
-                A.block_y[b] = (float *)take0(sizeof(float) * (size_t)n * s.c);
+                A.block_y[b] = cv0.take_n<float>((size_t)n * s.c);
                 A.block_saved_bytes[b] = ptv2_block_saved_bytes(n, s.k, s.c, s.g);
-                A.block_saved[b] = take0(A.block_saved_bytes[b]);
+                A.block_saved[b] = cv0.take(A.block_saved_bytes[b]);
             }
     }
     if (prefix_only) {
-        A.bytes = off;
-        A.bytes0 = off0;
+        A.bytes = cv.off;
+        A.bytes0 = prefix.off;
         return A;
     }
     for (int i = 0; i < S; ++i) {
         A.down[i] = linbn(M->down[i], M->level[i].n, true);
-        A.pooled[i] = (float *)take(sizeof(float) * (size_t)M->level[i + 1].n * M->down[i].cout);
-        A.arg[i] = (int *)take(sizeof(int) * (size_t)M->level[i + 1].n * M->down[i].cout);
+        A.pooled[i] = cv.take_n<float>((size_t)M->level[i + 1].n * M->down[i].cout);
+        A.arg[i] = cv.take_n<int>((size_t)M->level[i + 1].n * M->down[i].cout);
         A.up[i] = linbn(M->up[i], M->level[i + 1].n, true);
         A.up_skip[i] = linbn(M->up_skip[i], M->level[i].n, true);  // y = the unpool output (skip branch + unpooled rows)
     }
@@ -264,18 +252,18 @@ Arena carve(const ptv2_model *M, void *base, void *base0 = nullptr, bool split =
         const int n = M->level[s.level].n;
         for (int j = 0; j < s.depth; ++j) {
             const int b = s.first_block + j;
-            A.block_y[b] = (float *)take(sizeof(float) * (size_t)n * s.c);
+            A.block_y[b] = cv.take_n<float>((size_t)n * s.c);
             A.block_saved_bytes[b] = ptv2_block_saved_bytes(n, s.k, s.c, s.g);
             if (M->checkpoint) shared_saved = std::max(shared_saved, A.block_saved_bytes[b]);
-            else A.block_saved[b] = take(A.block_saved_bytes[b]);
+            else A.block_saved[b] = cv.take(A.block_saved_bytes[b]);
         }
     }
     if (M->checkpoint) {
-        char *region = take(shared_saved);
+        char *region = cv.take(shared_saved);
         for (int b = 0; b < M->num_blocks; ++b) A.block_saved[b] = region;
     }
-    A.bytes = off;
-    A.bytes0 = off0;
+    A.bytes = cv.off;
+    A.bytes0 = prefix.off;
     return A;
 }
 
@@ -292,9 +280,7 @@ struct Work {
 // prefix_only: the workspace of the forward's prefix (patch embedding + seq 0) -- a function of level 0 alone
 Work carve_work(const ptv2_model *M, void *base, bool prefix_only = false) {
     Work W{};
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += al(bytes); return r; };
+    PtvCarver cv{(char *)base, 0};
     const int S = M->num_stages;
     W.block_bytes = 0;
     size_t widest = 0;
@@ -312,9 +298,9 @@ Work carve_work(const ptv2_model *M, void *base, bool prefix_only = false) {
     };
     note(M->embed, M->level[0].n);
     if (prefix_only) {
-        W.block = take(W.block_bytes);
-        W.dense = take(W.dense_bytes);
-        W.bytes = off;
+        W.block = cv.take(W.block_bytes);
+        W.dense = cv.take(W.dense_bytes);
+        W.bytes = cv.off;
         return W;
     }
     if (!headless(M)) note(M->head, M->level[0].n);
@@ -326,19 +312,17 @@ Work carve_work(const ptv2_model *M, void *base, bool prefix_only = false) {
     if (!headless(M))
         W.dense_bytes = std::max(W.dense_bytes, dense_workspace_bytes(M->level[0].n, std::max(M->num_classes, M->head.cout),
                                                                       std::max(M->in_channels, M->head.cout)));
-    W.block = take(W.block_bytes);
-    W.dense = take(W.dense_bytes);
-    W.ga = (float *)take(sizeof(float) * widest);
-    W.gb = (float *)take(sizeof(float) * widest);
-    W.gc = (float *)take(sizeof(float) * widest);
+    W.block = cv.take(W.block_bytes);
+    W.dense = cv.take(W.dense_bytes);
+    W.ga = cv.take_n<float>(widest); W.gb = cv.take_n<float>(widest); W.gc = cv.take_n<float>(widest);
     for (int i = 0; i <= S; ++i) {
         const int c = i == 0 ? M->embed.cout : M->down[i - 1].cout;
-        W.gskip[i] = (float *)take(sizeof(float) * (size_t)M->level[i].n * c);
+        W.gskip[i] = cv.take_n<float>((size_t)M->level[i].n * c);
     }
     for (int q = 0; q <= 2 * S; ++q) {
         const ptv2_seq &s = M->seq[q];
         for (int j = 0; j < s.depth; ++j)
-            W.fold_scratch[s.first_block + j] = (float *)take(sizeof(float) * ptv2_gva_fold_scratch_floats(s.c, s.g));
+            W.fold_scratch[s.first_block + j] = cv.take_n<float>(ptv2_gva_fold_scratch_floats(s.c, s.g));
     }
     // per Block: six (n, c) gradient operands + the records of the five-product and of the grouped-projection weight gradient
     W.wdefer_bytes = ptv2_wgrad_defer_table_bytes();
@@ -346,13 +330,15 @@ Work carve_work(const ptv2_model *M, void *base, bool prefix_only = false) {
         const ptv2_seq &s = M->seq[q];
         const int n = M->level[s.level].n;
         for (int j = 0; j < s.depth; ++j)
-            W.wdefer_bytes += al(sizeof(float) * 6 * (size_t)n * s.c) + al(dense_workspace_bytes(n, 5 * s.c, s.c)) +
-                              al(dense_workspace_bytes(n, s.c, s.c)) + 2 * al(sizeof(float) * (size_t)n * s.g) +
-                              al(dense_workspace_bytes(n, 2 * s.g, s.c)) + 2048;
+            W.wdefer_bytes += ptv2_align256(sizeof(float) * 6 * (size_t)n * s.c) +
+                              ptv2_align256(dense_workspace_bytes(n, 5 * s.c, s.c)) +
+                              ptv2_align256(dense_workspace_bytes(n, s.c, s.c)) + 2 * ptv2_align256(sizeof(float) * (size_t)n * s.g) +
+                              ptv2_align256(dense_workspace_bytes(n, 2 * s.g, s.c)) + 2048;
     }
     {   // the Linear + BatchNorm layers between the stages: gh (n, cout) + records
         auto layer = [&](const ptv2_linbn &L, int n) {
-            W.wdefer_bytes += al(sizeof(float) * (size_t)n * L.cout) + al(dense_workspace_bytes(n, L.cout, L.cin)) + 512;
+            W.wdefer_bytes += ptv2_align256(sizeof(float) * (size_t)n * L.cout) +
+                              ptv2_align256(dense_workspace_bytes(n, L.cout, L.cin)) + 512;
         };
         layer(M->embed, M->level[0].n);
         if (!headless(M)) layer(M->head, M->level[0].n);
@@ -362,16 +348,10 @@ Work carve_work(const ptv2_model *M, void *base, bool prefix_only = false) {
             layer(M->up_skip[i], M->level[i].n);
         }
     }
-    W.wdefer = take(W.wdefer_bytes);
-    W.bytes = off;
+    W.wdefer = cv.take(W.wdefer_bytes);
+    W.bytes = cv.off;
     return W;
 }
-
-#define RUN(call)                        \
-    do {                                 \
-        int rc_ = (call);                \
-        if (rc_ != PTV2_OK) return rc_;  \
-    } while (0)
 
 std::atomic<int> g_wgrad_defer_mode{-1};  // -1: read AO_AMD_WGRAD_DEFER on first use; 0 off; 1 on
 bool wgrad_defer_enabled() {

@@ -16,8 +16,6 @@
 
 namespace {
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 constexpr int KMAX = 32;  // largest K of a self table handled here (the grid query's limit; PT-v2m2 uses 8 and 16)
 
 struct Ws {
@@ -54,27 +52,25 @@ bool geo_ok(const ptv2_scene_geo *G) {
 
 Ws carve_ws(const ptv2_scene_geo *G, void *base) {
     Ws w;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += al(bytes); return r; };
+    PtvCarver cv{(char *)base, 0};
     const int n0 = G->level[0].n, b = G->b;
     // every level has at most n0 points: the bounds below hold for all of them (checked again at run time)
     w.knn_bytes = knn_query_hip_workspace_bytes(n0, n0, b);
-    w.knn = take(w.knn_bytes);
+    w.knn = cv.take(w.knn_bytes);
     w.pool_bytes = grid_pool_hip_workspace_bytes(n0, b);
-    w.pool = take(w.pool_bytes);
+    w.pool = cv.take(w.pool_bytes);
     w.pos_bytes = gva_workspace_bytes(n0, KMAX, 8, 1);
-    w.pos = take(w.pos_bytes);
+    w.pos = cv.take(w.pos_bytes);
     {
         ptv2_inverse_job jobs[PTV2_INVERSE_MAX_JOBS];
         const int cnt = std::min(count_tables(G), (int)PTV2_INVERSE_MAX_JOBS);
         for (int j = 0; j < cnt; ++j) { jobs[j].n = n0; jobs[j].k = KMAX; jobs[j].idx = nullptr; jobs[j].inv_ptr = nullptr; jobs[j].inv_rows = nullptr; }
         w.inv_bytes = cnt ? inverse_tables_hip_workspace_bytes(cnt, jobs) : 0;
     }
-    w.inv = take(w.inv_bytes);
-    w.dist2 = (float *)take(sizeof(float) * (size_t)n0 * KMAX);
-    w.n_out = (int *)take(256);
-    w.bytes = off;
+    w.inv = cv.take(w.inv_bytes);
+    w.dist2 = cv.take_n<float>((size_t)n0 * KMAX);
+    w.n_out = (int *)cv.take(256);
+    w.bytes = cv.off;
     return w;
 }
 
@@ -82,15 +78,15 @@ Ws carve_ws(const ptv2_scene_geo *G, void *base) {
 size_t level_bytes(const ptv2_scene_geo *G, int i, size_t n, bool first, bool last) {
     size_t t = 0;
     const ptv2_geo_level &L = G->level[i];
-    if (!first) t += al(12 * n) + al(4 * (size_t)G->b);
+    if (!first) t += ptv2_align256(12 * n) + ptv2_align256(4 * (size_t)G->b);
     for (int j = 0; j < L.nk; ++j) {
         const size_t k = L.knn[j].k;
-        if (!first) t += al(4 * n * k) + al(24) + al(72);
-        t += al(4 * (n + 1)) + al(4 * n * k);
+        if (!first) t += ptv2_align256(4 * n * k) + ptv2_align256(24) + ptv2_align256(72);
+        t += ptv2_align256(4 * (n + 1)) + ptv2_align256(4 * n * k);
     }
     if (!last) {
-        t += al(8 * n) + al(4 * n) + al(4 * (n + 1));
-        if (G->interp) t += al(12 * n) + al(12 * n) + al(4 * (n + 1)) + al(12 * n);
+        t += ptv2_align256(8 * n) + ptv2_align256(4 * n) + ptv2_align256(4 * (n + 1));
+        if (G->interp) t += ptv2_align256(12 * n) + ptv2_align256(12 * n) + ptv2_align256(4 * (n + 1)) + ptv2_align256(12 * n);
     }
     return t;
 }
@@ -133,12 +129,6 @@ extern "C" size_t ptv2_scene_geometry_workspace_bytes(const ptv2_scene_geo *G) {
     return carve_ws(G, nullptr).bytes + 256;
 }
 
-#define RUN(call)                        \
-    do {                                 \
-        int rc_ = (call);                \
-        if (rc_ != PTV2_OK) return rc_;  \
-    } while (0)
-
 static int scene_geometry(ptv2_scene_geo *G, void *arena, size_t arena_bytes, void *workspace, size_t workspace_bytes, void *stream);
 
 extern "C" int ptv2_scene_geometry_hip_launcher(ptv2_scene_geo *G, void *arena, size_t arena_bytes, void *workspace,
@@ -162,7 +152,7 @@ static int scene_geometry(ptv2_scene_geo *G, void *arena, size_t arena_bytes, vo
     bool full = false;
     auto take = [&](size_t bytes) -> long long {
         const size_t at = off;
-        off += al(bytes);
+        off += ptv2_align256(bytes);
         if (off > arena_bytes) { full = true; return -1; }
         return (long long)at;
     };
@@ -209,7 +199,7 @@ static int scene_geometry(ptv2_scene_geo *G, void *arena, size_t arena_bytes, vo
             return PTV2_ERR_ARG;
         }
         N.n = m;
-        off = (size_t)N.coord + al(12 * (size_t)m);  // the pooled coordinates were the last item: give the unused rows back
+        off = (size_t)N.coord + ptv2_align256(12 * (size_t)m);  // the pooled coordinates were the last item: give the unused rows back
         coords[i + 1] = (const float *)at(N.coord);
         offsets[i + 1] = (const int *)at(N.offset);
         if (knn_query_hip_workspace_bytes(std::max(n, m), m, b) > W.knn_bytes) return PTV2_ERR_WORKSPACE;

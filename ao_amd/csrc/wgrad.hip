@@ -549,8 +549,6 @@ static bool wgrad_lds_shape_ok(int cout, int cin) { return cout % 4 == 0 && cin 
 constexpr size_t WL_LDS_BYTES = sizeof(float) * std::max<size_t>(4 * (size_t)WL_ROWS * WG_TILE,
                                                                  (size_t)(TPB / WAVE) * (WG_MT * WG_MT * 4 + WG_MT) * (WAVE + 1));
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace dense
 
 using namespace dense;
@@ -559,7 +557,7 @@ extern "C" size_t dense_workspace_bytes(int n, int cout, int cin) {  // cout*cin
     const size_t chunks = (size_t)(n + WG_CHUNK_MIN - 1) / WG_CHUNK_MIN + 1;
     const size_t wg = sizeof(float) * chunks * ((size_t)cout * cin + cout);
     const size_t bn = sizeof(float) * (size_t)MAX_BLK * 2 * (size_t)std::max(cout, cin);
-    return align_up(std::max(wg, bn)) + 1024;
+    return ptv2_align256(std::max(wg, bn)) + 1024;
 }
 
 // rows per split-K workgroup of the weight gradient
@@ -603,7 +601,7 @@ struct WgradDefer {
 };
 thread_local WgradDefer g_wdefer;
 constexpr int WGRAD_MAX_JOBS = 64;
-constexpr size_t WGRAD_TABLE_BYTES = (sizeof(WgradJob) * WGRAD_MAX_JOBS + 255) & ~(size_t)255;
+constexpr size_t WGRAD_TABLE_BYTES = ptv2_align256(sizeof(WgradJob) * WGRAD_MAX_JOBS);
 }  // namespace
 
 void ptv2_wgrad_defer_begin(void *arena, size_t bytes) {
@@ -627,7 +625,7 @@ size_t ptv2_wgrad_defer_table_bytes() { return WGRAD_FORMS * WGRAD_TABLE_BYTES; 
 // a slice of the arena that lives until the backward ends (operands a deferred job reads, its records); NULL: no room
 float *ptv2_wgrad_defer_alloc(size_t floats) {
     WgradDefer &D = g_wdefer;
-    const size_t bytes = (sizeof(float) * floats + 255) & ~(size_t)255;
+    const size_t bytes = ptv2_align256(sizeof(float) * floats);
     if (!D.active || D.used + bytes > D.cap) return nullptr;
     float *p = (float *)(D.arena + D.used);
     D.used += bytes;

@@ -369,6 +369,23 @@ int gva_block_forward_hip_launcher(const ptv2_gva_block *blk, void *workspace, s
 int gva_block_backward_hip_launcher(const ptv2_gva_block *blk, const ptv2_gva_block_grads *grads,
                                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* Host only (no device is touched): which kernel form each stage of a grouped-vector-attention call with these arguments
+ * runs under the current environment (ao_amd/csrc/gva_plan.h).  attn_drop: attention dropout is active; has_inverse: the
+ * inverse neighbour table is handed in.  Writes 12 ints to out (out_len >= 12, else PTV2_ERR_ARG):
+ *    0 logits_fwd        0 MFMA | 1 point | 2 rows
+ *    1 fwd               0 point | 1 tile | 2 staged            (softmax + aggregation + grouped projection)
+ *    2 softmax           0 point | 1 rows                       (inside the staged forward)
+ *    3 bwd_agg           0 tile | 1 point, g_A formed on chip | 2 point behind peb_bwd | 3 staged
+ *    4 bwd_agg_given_gA  2 | 3: the same for gva_aggregate_backward_hip_launcher, which is handed g_A / g_sw
+ *    5 logits_bwd        0 fused | 1 rows + point params | 2 rows + params
+ *    6 keeps_A           the forward writes A (n,g,c); ptv2_block_saved_bytes counts it
+ *    7 fused_peb         bwd_agg is 0 or 1: g_A / g_sw are not in gva_block_workspace_bytes, the inverse table is required
+ *    8 wp2_recompute     grad Wp2 from a weight gradient that forms A again (== !keeps_A)
+ *    9 bwd_takes_dropout a backward form that applies attention dropout exists
+ *   10 bwd_tile_shape    the backward tile kernel is instantiated for (k, c, g)
+ *   11 g_slot            0..4 for g = 6, 12, 24, 48, 64, else -1 */
+int ptv2_gva_plan_describe(int n, int k, int c, int g, int attn_drop, int has_inverse, int *out, int out_len);
+
 /* ---------------------------------------------------------- grid pooling --
  * Device pieces of GridPool.forward (point_transformer_v2m2_base.py:244-269), which the reference
  * builds from torch_scatter.segment_csr calls (third party, not vendored):
