@@ -1,0 +1,109 @@
+"""The ctypes side of include/ptv2_hip.h, derived from the header's text at import.
+
+The header is the contract and is written in a small, regular subset of C: `#define NAME integer`, anonymous enums,
+`typedef struct NAME {...} NAME;` and prototypes.  `parse()` reads exactly that and raises on anything else, so a
+constant, a struct layout or a launcher signature is written once, in the header:
+
+    consts      {name: int}                    every integer #define and enumerator
+    structs     {name: ctypes.Structure}       field for field, in header order
+    signatures  {name: (restype, argtypes)}    every prototype
+
+Pointers are c_void_p (callers pass tensor.data_ptr() / ctypes.addressof()), except `char *`, which is c_char_p.
+"""
+import ctypes
+import os
+import re
+
+HEADER = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "ptv2_hip.h"))
+
+_VALUES = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double,
+           "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t}
+_POINTEES = ("void", "char", "unsigned long long")  # known behind a star only
+_TYPE = re.compile(r"\s*(unsigned\s+long\s+long|long\s+long|unsigned\b|\w+)(.*)", re.S)
+_DECLARATOR = re.compile(r"\s*((?:\*\s*)*)(\w+)\s*(?:\[([^\]]*)\])?\s*")
+_ITEM = re.compile(r"""
+    ^[ \t]*\#[ \t]*define[ \t]+(?P<define>\w+)[ \t]+(?P<value>\S.*?)[ \t]*$
+  | ^[ \t]*\#[ \t]*(?:include\b.*|ifndef\b.*|endif\b.*|define[ \t]+\w+[ \t]*)$
+  | \benum\s*\{(?P<enum>[^{}]*)\}\s*;
+  | \btypedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<fields>[^{}]*)\}\s*(?P<struct>\w+)\s*;
+  | (?P<result>[\w\s*]+?)\b(?P<function>\w+)\s*\((?P<params>[^(){};]*)\)\s*;
+""", re.M | re.X)
+
+
+def _const_expr(text, consts, where):
+    expr = re.sub(r"[A-Za-z_]\w*", lambda m: str(consts[m.group()]) if m.group() in consts else m.group(), text)
+    if not re.fullmatch(r"[\d\s+\-*()]+", expr):
+        raise RuntimeError("ao_amd: %s: `%s` is not an integer constant expression of known names" % (where, text.strip()))
+    try:
+        return int(eval(expr, {"__builtins__": {}}))  # (digits, + - * and parentheses only: checked above)
+    except SyntaxError:
+        raise RuntimeError("ao_amd: %s: cannot evaluate `%s`" % (where, text.strip())) from None
+
+
+def _declarations(text, structs, consts, where, fields):
+    """`const float *q, *key[2]` -> [("q", c_void_p), ("key", c_void_p * 2)]: one type, one or more declarators.  In a
+    parameter list (fields False) an array is the pointer it decays to and a struct cannot be passed by value."""
+    m = _TYPE.match(re.sub(r"\b(const|volatile)\b", " ", text))
+    base = " ".join(m.group(1).split()) if m else None
+    out = []
+    for decl in m.group(2).split(",") if m else [""]:
+        d = _DECLARATOR.fullmatch(decl)
+        if d is None:
+            raise RuntimeError("ao_amd: %s: cannot read the declaration `%s`" % (where, " ".join(text.split())))
+        stars, name, bound = d.group(1).count("*"), d.group(2), d.group(3)
+        value = _VALUES.get(base) or (structs.get(base) if fields else None)
+        if stars or (bound is not None and not fields):
+            if value is None and base not in _POINTEES and base not in structs:
+                raise RuntimeError("ao_amd: %s: unknown type `%s` of `%s`" % (where, base, name))
+            ctype = ctypes.c_char_p if (base, stars, bound) == ("char", 1, None) else ctypes.c_void_p
+        elif value is None:
+            raise RuntimeError("ao_amd: %s: no ctypes type for `%s` of `%s`" % (where, base, name))
+        else:
+            ctype = value
+        if bound is not None and fields:
+            ctype = ctype * _const_expr(bound, consts, "%s, bound of `%s`" % (where, name))
+        out.append((name, ctype))
+    return out
+
+
+def parse(text):
+    """(consts, structs, signatures) of a header in the subset described above."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b.*?$", " ", text, flags=re.S | re.M)
+    consts, structs, signatures = {}, {}, {}
+    at = 0
+    for m in _ITEM.finditer(text):
+        if text[at:m.start()].strip():
+            break
+        at = m.end()
+        if m.group("define"):
+            consts[m.group("define")] = _const_expr(m.group("value"), consts, "#define " + m.group("define"))
+        elif m.group("enum") is not None:
+            value = -1
+            for item in filter(None, (i.strip() for i in m.group("enum").split(","))):
+                name, _, init = (s.strip() for s in item.partition("="))
+                value = _const_expr(init, consts, "enumerator " + name) if init else value + 1
+                consts[name] = value
+        elif m.group("struct"):
+            name = m.group("struct")
+            if name != m.group("tag"):
+                raise RuntimeError("ao_amd: typedef struct %s is named %s" % (m.group("tag"), name))
+            fields = [f for line in m.group("fields").split(";") if line.strip()
+                      for f in _declarations(line, structs, consts, "struct " + name, True)]
+            structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+        elif m.group("function"):
+            name, params = m.group("function"), m.group("params").strip()
+            where = "prototype of " + name
+            (_, restype), = _declarations(m.group("result") + " result", structs, consts, where, False)
+            signatures[name] = (restype, [] if params in ("", "void") else [
+                ctype for p in params.split(",") for _, ctype in _declarations(p, structs, consts, where, False)])
+    rest = text[at:].strip()
+    if rest:
+        raise RuntimeError("ao_amd: cannot read this declaration of the C header: `%s`" % " ".join(rest.split())[:160])
+    return consts, structs, signatures
+
+
+if not os.path.exists(HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % HEADER)
+with open(HEADER) as _f:
+    consts, structs, signatures = parse(_f.read())

@@ -11,40 +11,12 @@ import ctypes
 
 import torch
 
-from .. import _lib
+from .. import _abi, _lib
 from . import gva as _gva
 
-NPARAM, NBN = 30, 7
-_P = ctypes.c_void_p
-
-_lib.register({
-    "rows_gemm_hip_launcher": (_lib._c_int, [_lib._c_int] * 3 + [_lib._vp, _lib._vp, _lib._c_int, _lib._vp, _lib._vp,
-                                                                 _lib._c_int, _lib._vp]),
-    "rows_gemm_multi_hip_launcher": (_lib._c_int, [_lib._c_int] * 5 + [_lib._vp, _lib._vp, _lib._c_int, _lib._vp, _lib._vp,
-                                                                       _lib._c_int, _lib._vp]),
-    "rows_gemm_fused_hip_launcher": (_lib._c_int, [_lib._c_int] * 5 + [_lib._vp, _lib._vp, _lib._c_int, _lib._vp, _lib._vp,
-                                                                       _lib._c_int, _lib._vp, _lib._vp, _lib._vp, _lib._vp]),
-    "ptv2_block_saved_bytes": (_lib._c_size, [_lib._c_int] * 4),
-    "ptv2_block_workspace_bytes": (_lib._c_size, [_lib._c_int] * 4),
-    "ptv2_block_param_layout": (_lib._c_int, [_lib._c_int, _lib._c_int, _lib._vp]),
-    "ptv2_block_forward_hip_launcher": (_lib._c_int, [_lib._vp, _lib._vp, _lib._c_size, _lib._vp]),
-    "ptv2_block_backward_hip_launcher": (_lib._c_int, [_lib._vp, _lib._vp, _lib._vp, _lib._c_size, _lib._vp]),
-})
-
-
-class _Blk(ctypes.Structure):  # mirrors ptv2_block
-    _fields_ = ([(n_, ctypes.c_int) for n_ in ("n", "k", "c", "g", "training")]
-                + [("eps", ctypes.c_float), ("momentum", ctypes.c_float)]
-                + [(n_, _P) for n_ in ("x", "coord", "idx", "mu", "cov", "rowscale")]
-                + [("param", _P * NPARAM), ("run_mean", _P * NBN), ("run_var", _P * NBN), ("batches", _P * NBN),
-                   ("y", _P), ("saved", _P), ("saved_bytes", ctypes.c_size_t), ("matmul_bf16", ctypes.c_int),
-                   ("attn_drop_p", ctypes.c_float), ("attn_drop_seed", ctypes.c_uint)])
-
-
-class _BlkGrads(ctypes.Structure):  # mirrors ptv2_block_grads
-    _fields_ = [(n_, _P) for n_ in ("gy", "inv_ptr", "inv_rows", "gx", "gparam")] + [("gp", _P * NPARAM)]
-
-
+NPARAM, NBN = _abi.consts["PTV2_BLK_NPARAM"], _abi.consts["PTV2_BLK_NBN"]
+_Blk = _abi.structs["ptv2_block"]
+_BlkGrads = _abi.structs["ptv2_block_grads"]
 _lib.check_struct(0, _Blk)
 _lib.check_struct(1, _BlkGrads)
 

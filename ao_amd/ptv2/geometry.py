@@ -14,7 +14,7 @@ from typing import List, Optional
 
 import torch
 
-from .. import _lib, pointops
+from .. import _abi, _lib, pointops
 from ..pointops.interpolation import interpolation_index_weight
 from ..pointops.query import KnnGrid, knn_query_dist2
 
@@ -203,32 +203,9 @@ def finish_geometry(st, before_inverse=None):
 
 
 # ---- the second half as ONE native call (ao_amd/csrc/scene.hip) --------------------------------------------------------------
-_MAX_STAGES, _GEO_MAX_K = 5, 2
-_LL = ctypes.c_longlong
-
-
-class _GeoTable(ctypes.Structure):  # mirrors ptv2_geo_table
-    _fields_ = [("k", ctypes.c_int)] + [(n, _LL) for n in ("idx", "mu", "cov", "inv_ptr", "inv_rows")]
-
-
-class _GeoLevel(ctypes.Structure):  # mirrors ptv2_geo_level
-    _fields_ = ([("n", ctypes.c_int), ("nk", ctypes.c_int), ("knn", _GeoTable * _GEO_MAX_K)]
-                + [(n, _LL) for n in ("coord", "offset", "cluster", "order", "idx_ptr", "up_idx", "up_w", "up_inv_ptr", "up_inv_rows")])
-
-
-class _SceneGeo(ctypes.Structure):  # mirrors ptv2_scene_geo
-    _fields_ = [("num_stages", ctypes.c_int), ("b", ctypes.c_int), ("interp", ctypes.c_int), ("grid_size", ctypes.c_float * _MAX_STAGES),
-                ("coord0", ctypes.c_void_p), ("offset0", ctypes.c_void_p), ("knn0", ctypes.c_void_p * _GEO_MAX_K),
-                ("fwd_ready_event", ctypes.c_void_p), ("knn0_event", ctypes.c_void_p), ("level", _GeoLevel * (_MAX_STAGES + 1)),
-                ("sizes_ready", ctypes.c_int), ("fwd_recorded", ctypes.c_int)]
-
-
-_lib.register({
-    "ptv2_scene_geometry_arena_bytes": (_lib._c_size, [ctypes.c_void_p]),
-    "ptv2_scene_geometry_workspace_bytes": (_lib._c_size, [ctypes.c_void_p]),
-    "ptv2_scene_geometry_hip_launcher": (_lib._c_int, [ctypes.c_void_p, ctypes.c_void_p, _lib._c_size, ctypes.c_void_p, _lib._c_size,
-                                                       ctypes.c_void_p]),
-})
+_MAX_STAGES, _GEO_MAX_K = _abi.consts["PTV2_MAX_STAGES"], _abi.consts["PTV2_GEO_MAX_K"]
+_GeoTable, _GeoLevel = _abi.structs["ptv2_geo_table"], _abi.structs["ptv2_geo_level"]
+_SceneGeo = _abi.structs["ptv2_scene_geo"]
 _lib.check_struct(4, _SceneGeo)
 
 

@@ -28,37 +28,8 @@ import os
 
 import torch
 
-from .. import _lib
+from .. import _abi, _lib
 from .layers import skinny_linear
-
-_SIG = {
-    "gva_pos_stats_hip_launcher": (_lib._c_int, [_lib._c_int] * 2 + [_lib._vp] * 5 + [_lib._c_size, _lib._vp]),
-    "gva_pos_moments_hip_launcher": (_lib._c_int, [_lib._c_int] * 2 + [_lib._vp] * 5 + [_lib._c_size, _lib._vp]),
-    "gva_logits_forward_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 12 + [_lib._c_size, _lib._vp]),
-    "gva_logits_backward_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 18 + [_lib._c_size, _lib._vp]),
-    "gva_aggregate_workspace_bytes": (_lib._c_size, [_lib._c_int] * 4),
-    "gva_aggregate_forward_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 14 + [_lib._vp]),
-    "gva_aggregate_backward_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 25 + [_lib._c_size, _lib._vp]),
-    "gva_workspace_bytes": (_lib._c_size, [_lib._c_int] * 4),
-    "gva_fold_p_forward_hip_launcher": (_lib._c_int, [_lib._c_int] + [_lib._vp] * 9 + [_lib._c_int, ctypes.c_double,
-                                                                               ctypes.c_float, ctypes.c_float]
-                                        + [_lib._vp] * 4),
-    "gva_fold_p_backward_hip_launcher": (_lib._c_int, [_lib._c_int] + [_lib._vp] * 7 + [_lib._c_int] + [_lib._vp] * 7),
-    "gva_fold_w_forward_hip_launcher": (_lib._c_int, [_lib._c_int] + [_lib._vp] * 7 + [_lib._c_int, ctypes.c_double,
-                                                                               ctypes.c_float, ctypes.c_float]
-                                        + [_lib._vp] * 5),
-    "gva_fold_w_backward_hip_launcher": (_lib._c_int, [_lib._c_int] + [_lib._vp] * 3 + [_lib._c_int, ctypes.c_double]
-                                         + [_lib._vp] * 7),
-    "gva_block_workspace_bytes": (_lib._c_size, [_lib._c_int] * 4),
-    "gva_block_forward_hip_launcher": (_lib._c_int, [_lib._vp, _lib._vp, _lib._c_size, _lib._vp]),
-    "gva_block_backward_hip_launcher": (_lib._c_int, [_lib._vp, _lib._vp, _lib._vp, _lib._c_size, _lib._vp]),
-    "gva_peb_forward_hip_launcher": (_lib._c_int, [_lib._c_int] * 3 + [_lib._vp] * 7),
-    "gva_peb_backward_hip_launcher": (_lib._c_int, [_lib._c_int] * 3 + [_lib._vp] * 6),
-    "gva_attention_forward_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 17),
-    "gva_attention_backward_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 25 + [_lib._c_size, _lib._vp]),
-    "gva_attention_wgrad_hip_launcher": (_lib._c_int, [_lib._c_int] * 4 + [_lib._vp] * 10 + [_lib._c_size, _lib._vp]),
-}
-_lib.register(_SIG)
 
 
 # ------------------------------------------------------------------ HIP stages --
@@ -117,12 +88,8 @@ def _f32c(t):
     return t.detach().float().contiguous()
 
 
-class _InverseJob(ctypes.Structure):  # mirrors ptv2_inverse_job (include/ptv2_hip.h)
-    _fields_ = [("n", ctypes.c_int), ("k", ctypes.c_int), ("idx", ctypes.c_void_p), ("inv_ptr", ctypes.c_void_p),
-                ("inv_rows", ctypes.c_void_p)]
-
-
-INVERSE_MAX_JOBS = 16  # PTV2_INVERSE_MAX_JOBS
+_InverseJob = _abi.structs["ptv2_inverse_job"]
+INVERSE_MAX_JOBS = _abi.consts["PTV2_INVERSE_MAX_JOBS"]
 
 
 def _cached_inverse(idx):
@@ -441,28 +408,9 @@ class _PebProject(torch.autograd.Function):
 
 
 # ------------------------------------------------------- whole block, one call --
-_P = ctypes.c_void_p
-
-
-class _BlockArgs(ctypes.Structure):  # mirrors ptv2_gva_block (include/ptv2_hip.h)
-    _fields_ = ([(n_, ctypes.c_int) for n_ in ("n", "k", "c", "g", "training")]
-                + [(n_, ctypes.c_float) for n_ in ("eps_p", "momentum_p", "eps_w", "momentum_w")]
-                + [(n_, _P) for n_ in (
-                    "q", "key", "v", "coord", "idx", "mu", "cov",
-                    "Wp1", "bp1", "gamma_p", "beta_p", "Wp2", "bp2", "Ww1", "bw1", "gamma_w", "beta_w", "Ww2", "bw2",
-                    "run_mean_p", "run_var_p", "run_mean_w", "run_var_w", "batches_p", "batches_w",
-                    "out", "a", "b", "rstd_p", "M", "cW", "kW", "qW", "W1", "w", "A", "sw", "sc", "sh",
-                    "mean_w", "rstd_w", "q_sc", "q_sh", "k_sc", "k_sh")]
-                + [("attn_drop_p", ctypes.c_float), ("attn_drop_seed", ctypes.c_uint)])
-
-
-_lib.check_struct(3, _BlockArgs)  # (the mirror must have the size the library was compiled with)
-
-
-class _BlockGrads(ctypes.Structure):  # mirrors ptv2_gva_block_grads
-    _fields_ = [(n_, _P) for n_ in (
-        "g_out", "inv_ptr", "inv_rows", "gq", "gk", "gv", "gWp1", "gbp1", "ggamma_p", "gbeta_p", "gWp2", "gbp2",
-        "gWw1", "gbw1", "ggamma_w", "gbeta_w", "gWw2", "gbw2")]
+_BlockArgs = _abi.structs["ptv2_gva_block"]
+_BlockGrads = _abi.structs["ptv2_gva_block_grads"]
+_lib.check_struct(3, _BlockArgs)  # (the library must have been compiled with the header the structs are read from)
 
 
 def _momentum(bn):

@@ -20,57 +20,14 @@ import os
 
 import torch
 
-from .. import _lib
+from .. import _abi, _lib
 from . import block as _block
 from . import gva as _gva
 
-_P, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-MAX_STAGES, MAX_BLOCKS = 5, 40
+MAX_STAGES, MAX_BLOCKS = _abi.consts["PTV2_MAX_STAGES"], _abi.consts["PTV2_MAX_BLOCKS"]
 NPARAM, NBN = _block.NPARAM, _block.NBN
-
-
-class _LinBn(ctypes.Structure):  # mirrors ptv2_linbn
-    _fields_ = [("cin", _I), ("cout", _I)] + [(n, _P) for n in ("w", "b", "gamma", "beta", "run_mean", "run_var", "batches",
-                                                                 "gw", "gb", "ggamma", "gbeta")]
-
-
-class _Level(ctypes.Structure):  # mirrors ptv2_level
-    _fields_ = [("n", _I), ("b", _I)] + [(n, _P) for n in ("coord", "offset", "order", "idx_ptr", "cluster", "up_idx", "up_w",
-                                                            "up_inv_ptr", "up_inv_rows")]
-
-
-class _Seq(ctypes.Structure):  # mirrors ptv2_seq
-    _fields_ = [(n, _I) for n in ("level", "depth", "first_block", "c", "g", "k")] + [(n, _P) for n in ("idx", "mu", "cov", "inv_ptr",
-                                                                                                       "inv_rows")]
-
-
-class _MBlock(ctypes.Structure):  # mirrors ptv2_model_block
-    _fields_ = [("param", _P * NPARAM), ("run_mean", _P * NBN), ("run_var", _P * NBN), ("batches", _P * NBN),
-                ("gparam", _P * NPARAM), ("rowscale", _P), ("attn_drop_p", _F), ("attn_drop_seed", ctypes.c_uint)]
-
-
-class _Model(ctypes.Structure):  # mirrors ptv2_model
-    _fields_ = ([(n, _I) for n in ("num_stages", "in_channels", "num_classes", "training", "interp")]
-                + [("eps", _F), ("momentum", _F), ("level", _Level * (MAX_STAGES + 1)), ("seq", _Seq * (2 * MAX_STAGES + 1)),
-                   ("num_blocks", _I), ("block", _MBlock * MAX_BLOCKS), ("embed", _LinBn), ("down", _LinBn * MAX_STAGES),
-                   ("up", _LinBn * MAX_STAGES), ("up_skip", _LinBn * MAX_STAGES), ("head", _LinBn)]
-                + [(n, _P) for n in ("head_w", "head_b", "g_head_w", "g_head_b", "feat", "logits", "saved")]
-                + [("saved_bytes", ctypes.c_size_t), ("matmul_bf16", _I), ("checkpoint", _I),
-                   ("decoder_done_event", _P), ("saved0", _P), ("saved0_bytes", ctypes.c_size_t)])
-
-
-_lib.register({
-    "ptv2_model_saved_bytes": (_lib._c_size, [_P]),
-    "ptv2_model_workspace_bytes": (_lib._c_size, [_P]),
-    "ptv2_model_forward_hip_launcher": (_lib._c_int, [_P, _P, _lib._c_size, _P]),
-    "ptv2_model_backward_hip_launcher": (_lib._c_int, [_P, _P, _P, _lib._c_size, _P]),
-    "ptv2_model_prefix_saved_bytes": (_lib._c_size, [_P]),
-    "ptv2_model_prefix_workspace_bytes": (_lib._c_size, [_P]),
-    "ptv2_model_forward_prefix_hip_launcher": (_lib._c_int, [_P, _P, _lib._c_size, _P]),
-    "ptv2_model_forward_rest_hip_launcher": (_lib._c_int, [_P, _P, _lib._c_size, _P]),
-})
-
-
+_LinBn, _Level, _Seq = _abi.structs["ptv2_linbn"], _abi.structs["ptv2_level"], _abi.structs["ptv2_seq"]
+_MBlock, _Model = _abi.structs["ptv2_model_block"], _abi.structs["ptv2_model"]
 _lib.check_struct(2, _Model)
 
 

@@ -39,6 +39,8 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert not missing, "declared in the header but not bound in ao_amd/_lib.py: %s" % missing
     extra = [n for n in lib._SIGNATURES if n not in names]
     assert not extra, "bound but not declared in include/ptv2_hip.h: %s" % extra
+    for n in lib._SIGNATURES:  # (the binding table is every prototype of the header, whatever its suffix)
+        assert hasattr(handle, n), "missing export: " + n
 
 
 def test_host_only_entry_points(lib):
