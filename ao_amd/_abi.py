@@ -107,3 +107,10 @@ if not os.path.exists(HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % HEADER)
 with open(HEADER) as _f:
     consts, structs, signatures = parse(_f.read())
+
+# the second public header (the input pipeline's augmentation launchers), read the same way into tables of its own
+DATA_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_data_hip.h")
+if not os.path.exists(DATA_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % DATA_HEADER)
+with open(DATA_HEADER) as _f:
+    data_consts, data_structs, data_signatures = parse(_f.read())

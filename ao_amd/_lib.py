@@ -26,6 +26,8 @@ _lib = None
 # include/ptv2_hip.h changes (_abi.py derives the ctypes side from the header as it is now; the library holds the header it
 # was compiled with): a stale libptv2_hip.so then refuses to load instead of misreading memory
 EXPECTED_ABI = 11
+# the same for include/ptv2_data_hip.h and ptv2_data_abi_version() (ao_amd/csrc/augment.hip)
+EXPECTED_DATA_ABI = 1
 
 
 def build(verbose=False):
@@ -43,14 +45,27 @@ def lib():
                 "ao_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C ao_amd/csrc` (needs hipcc). There is no CPU fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the symbol is missing: loud by design
-            fn.restype = res
-            fn.argtypes = args
+        for table in (_SIGNATURES, _abi.data_signatures):
+            for name, (res, args) in table.items():
+                try:
+                    fn = getattr(handle, name)
+                except AttributeError:  # a missing symbol is loud by design
+                    raise RuntimeError("ao_amd: %s has no `%s` -- stale build; rebuild with `make -C ao_amd/csrc`"
+                                       % (LIB_PATH, name)) from None
+                fn.restype = res
+                fn.argtypes = args
         have = handle.ptv2_abi_version()
         if have != EXPECTED_ABI:
             raise RuntimeError("ao_amd: %s has ABI version %d, the python side expects %d -- stale build; rebuild with "
                                "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_ABI))
+        have = handle.ptv2_data_abi_version()
+        if have != EXPECTED_DATA_ABI:
+            raise RuntimeError("ao_amd: %s has data ABI version %d, the python side expects %d -- stale build; rebuild with "
+                               "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_DATA_ABI))
+        for which, name in enumerate(("ptv2_aug_step", "ptv2_aug_program")):
+            if handle.ptv2_data_struct_bytes(which) != ctypes.sizeof(_abi.data_structs[name]):
+                raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (
+                    name, ctypes.sizeof(_abi.data_structs[name]), handle.ptv2_data_struct_bytes(which), LIB_PATH))
         _lib = handle
     return _lib
 

@@ -176,7 +176,7 @@ const char *kNames[KID_COUNT] = {
     "attention_fwd_tile_kernel<12, 96, 12>", "attention_fwd_tile_kernel<24, 192, 12>", "attention_fwd_tile_kernel<48, 384, 12>",
     "attention_fwd_tile_kernel<64, 512, 16>", "wp2_wgrad_tile_kernel_jobs",
     "attention_bwd_tile_kernel<12, 96, 8>", "attention_bwd_tile_kernel<24, 192, 8>", "attention_bwd_tile_kernel<48, 384, 8>",
-    "attention_bwd_tile_kernel<64, 512, 8>"};
+    "attention_bwd_tile_kernel<64, 512, 8>", "aug_points_kernel"};
 struct Rec { hipEvent_t a, b; double bytes; };
 std::mutex g_mu;
 int g_on = 0;

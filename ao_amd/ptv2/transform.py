@@ -19,15 +19,36 @@ that GridSample sees fp32 as everywhere else in this module: the coordinates equ
 Where the reference's result depends on numpy's unstable argsort (which point of a voxel a given draw selects, the
 order of equidistant points) the order here is the stable one -- ascending original index among equals.  Random
 choices come from a torch.Generator (or are passed in), not from numpy's global RNG.
+
+The training augmentations (Copy :54, RandomShift :146, PointClip :160, RandomRotate :209, RandomJitter :319,
+ChromaticAutoContrast :358, ChromaticTranslation :379, ChromaticJitter :392, RandomColorDrop :692, ElasticDistortion :709,
+ShufflePoint :1002) and the Mix3D switch of the collate (datasets/utils.py:43-54) are here as well.  The per-point ones do
+not compute in torch: each class describes itself as step records (`steps(draws)`), `fuse_plan` turns the records of one or
+of many consecutive transforms into segments of a program (include/ptv2_data_hip.h), and ao_amd/csrc/augment.hip runs a
+segment once per point in one kernel.  Calling a class on its own runs a one-transform program through the same kernel.
+A tensor's dtype is the reference's array dtype: `coord` is float32 until the first applied rotation (or PointClip) and
+float64 afterwards, so a class called alone on a float32 coord returns what numpy returns, float64 included;
+`Compose(cfg, fuse=True)` carries float64 between its segments and rounds to float32 once at the end of each run of
+per-point transforms.  Every host-side random decision (gate, angle, scale, blend, translation, permutation) comes from a
+torch.Generator or is passed by keyword; per-point normals come from a 64-bit `seed` (in-kernel Philox4x32-10, counter =
+point index and the step's stream number) or from a `noise=` tensor.
+
+Not here, on purpose: RandomDropout, HueSaturationTranslation, RandomColorJitter / RandomColorGrayScale (commented out in
+every PT-v2m2 config, or active only in one ScanNet list with a ratio the data-efficient benchmarks use), NormalizeCoord,
+PositiveShift, CropBoundary and the contrastive / instance transforms (ContrastiveViewsGenerator, InstanceParser), which
+belong to other model families.
 """
 import copy
+import ctypes
+import inspect
 import math
 
 import torch
 
-from .. import _lib
+from .. import _abi, _lib
 
 _SIGN = -(1 << 63)
+_K = _abi.data_consts
 
 
 def _dev_f32(x):
@@ -231,6 +252,12 @@ class CenterShift:
             data_dict["coord"] = coord - shift
         return data_dict
 
+    def draw(self, generator=None):
+        return {}
+
+    def steps(self, draws=None):
+        return [dict(kind=_K["PTV2_AUG_CENTER_SHIFT"], flags=_K["PTV2_AUG_FLAG_APPLY_Z"] if self.apply_z else 0, bounds="coord")]
+
 
 class NormalizeColor:
     def __call__(self, data_dict):
@@ -261,6 +288,13 @@ class RandomScale:
             data_dict["coord"] = (coord.double() * scale).to(coord.dtype)  # a float64 product rounded once, as numpy's *=
         return data_dict
 
+    def draw(self, generator=None):
+        return dict(scale=_uniform(self.scale[0], self.scale[1], 3 if self.anisotropic else 1, generator).tolist())
+
+    def steps(self, draws):
+        s = [float(v) for v in torch.as_tensor(draws["scale"], dtype=torch.float64).reshape(-1).tolist()]
+        return [dict(kind=_K["PTV2_AUG_SCALE"], p=s * 3 if len(s) == 1 else s)]
+
 
 class RandomFlip:
     def __init__(self, p=0.5):
@@ -277,6 +311,13 @@ class RandomFlip:
                         v[:, axis] = -v[:, axis]
                         data_dict[key] = v
         return data_dict
+
+    def draw(self, generator=None):
+        return dict(draws=torch.rand(2, dtype=torch.float64, generator=generator).tolist())
+
+    def steps(self, draws):
+        sign = [-1.0 if u < self.p else 1.0 for u in draws["draws"]] + [1.0]
+        return [dict(kind=_K["PTV2_AUG_SCALE"], p=sign, normal=True)] if -1.0 in sign else []
 
 
 class RandomRotateTargetAngle:
@@ -317,6 +358,20 @@ class RandomRotateTargetAngle:
             data_dict["normal"] = (normal.double() @ self.matrix(angle).to(normal.device).t()).to(normal.dtype)
         return data_dict
 
+    def draw(self, generator=None):
+        gate = float(torch.rand((), dtype=torch.float64, generator=generator))
+        if gate > self.p:
+            return dict(gate=gate, angle=None)
+        return dict(gate=gate, angle=self.angle[int(torch.randint(0, len(self.angle), (), generator=generator))])
+
+    def steps(self, draws):
+        if draws["gate"] > self.p:
+            return []
+        step = dict(kind=_K["PTV2_AUG_ROTATE"], p=self.matrix(draws["angle"]).reshape(-1).tolist(), normal=True)
+        if self.center is None:
+            return [dict(step, flags=_K["PTV2_AUG_FLAG_BOUNDS_CENTER"], bounds="coord", p=step["p"] + [0.0] * 3)]
+        return [dict(step, p=step["p"] + [float(v) for v in self.center])]
+
 
 class ToTensor:
     """The data is tensors already: a pass-through (numpy arrays, which the reference converts here, are converted too)."""
@@ -343,17 +398,68 @@ def build_transform(cfg):
     cls = _TRANSFORMS.get(kind)
     if cls is None:
         raise KeyError("%s is not a transform of ao_amd.ptv2.transform (%s)" % (kind, sorted(_TRANSFORMS)))
+    missing = [name for name, p in inspect.signature(cls).parameters.items()
+               if p.default is p.empty and p.kind == p.POSITIONAL_OR_KEYWORD and name not in args]
+    if missing:  # a config that leaves out a key its class needs is a KeyError too, naming the key
+        raise KeyError("%s needs the config key(s) %s" % (kind, ", ".join(missing)))
     return cls(**args)
 
 
 class Compose:
-    def __init__(self, cfg=None):
+    """fuse=False: the transforms one after the other, as the reference's Compose.  fuse=True: every run of consecutive
+    per-point transforms (those with `steps`) becomes one program (`fuse_plan`), carried in float64 between its segments and
+    rounded to float32 at its end; the other transforms (GridSample, SphereCrop, ShufflePoint, Copy, NormalizeColor,
+    ToTensor, Collect) run between the programs as they do unfused.  The host-side decisions (gates, angles, the seed of
+    the per-point normals, ShufflePoint's permutation) come from `generator`; GridSample and SphereCrop draw on the device
+    and take `device_generator` (a CUDA generator; None: torch's global one)."""
+
+    def __init__(self, cfg=None, fuse=False, generator=None, device_generator=None):
         self.cfg = cfg if cfg is not None else []
         self.transforms = [t if callable(t) else build_transform(t) for t in self.cfg]
+        self.fuse, self.generator, self.device_generator = fuse, generator, device_generator
 
-    def __call__(self, data_dict):
-        for t in self.transforms:
-            data_dict = t(data_dict)
+    def groups(self):
+        """[(is a per-point run, [indices into self.transforms])]"""
+        out = []
+        for i, t in enumerate(self.transforms):
+            pointwise = hasattr(t, "steps")
+            if pointwise and out and out[-1][0]:
+                out[-1][1].append(i)
+            else:
+                out.append((pointwise, [i]))
+        return out
+
+    def draw(self):
+        """one draw per transform (None for those that are not per-point) and the seed of the per-point normals"""
+        seed = int(torch.randint(0, 1 << 62, (), generator=self.generator))
+        return dict(seed=seed, per=[t.draw(self.generator) if hasattr(t, "steps") else None for t in self.transforms])
+
+    def records(self, indices, draws):
+        out = []
+        for i in indices:
+            for rec in self.transforms[i].steps(draws["per"][i]):
+                out.append(dict(rec, stream=_STREAMS * i + rec.get("stream", 0)))
+        return out
+
+    def plan(self, draws, in_f64=False):
+        """the segments of every per-point run for these draws: host only"""
+        return [fuse_plan(self.records(idx, draws), in_f64=in_f64, final_round=True) for pointwise, idx in self.groups() if pointwise]
+
+    def __call__(self, data_dict, draws=None):
+        if not self.fuse:
+            for t in self.transforms:
+                data_dict = t(data_dict)
+            return data_dict
+        if draws is None:
+            draws = self.draw()
+        for pointwise, idx in self.groups():
+            if pointwise:
+                data_dict = _run_records(self.records(idx, draws), data_dict, draws["seed"], final_round=True)
+                continue
+            t = self.transforms[idx[0]]
+            g = self.generator if isinstance(t, ShufflePoint) else self.device_generator
+            takes = g is not None and "generator" in inspect.signature(t.__call__).parameters
+            data_dict = t(data_dict, generator=g) if takes else t(data_dict)
         return data_dict
 
 
@@ -381,14 +487,352 @@ def test_fragments(data_dict, test_cfg, transform=None):
 
 test_fragments.__test__ = False  # (a library function, not a pytest case, whatever module imports it)
 
+# ------------------------------------------------------------------------------------------ training augmentations --
+_STREAMS = 8  # RNG stream numbers per transform of a list: transform i owns [8 i, 8 i + 8)
+_COORD_KINDS = tuple(_K[k] for k in ("PTV2_AUG_CENTER_SHIFT", "PTV2_AUG_ROTATE", "PTV2_AUG_SCALE", "PTV2_AUG_SHIFT",
+                                     "PTV2_AUG_CLIP", "PTV2_AUG_JITTER", "PTV2_AUG_ELASTIC"))
+_TO_F64 = (_K["PTV2_AUG_ROTATE"], _K["PTV2_AUG_CLIP"])  # np.dot / np.clip with list bounds return a float64 array
+_NOISE_KINDS = (_K["PTV2_AUG_JITTER"], _K["PTV2_AUG_COLOR_JITTER"])
+_ROUND = _K["PTV2_AUG_ROUND_F32"]
+
+
+def fuse_plan(records, in_f64=False, final_round=False):
+    """Step records -> segments of one program each: [dict(bounds=bool, readback=bool, steps=[...], out_f64=bool)].
+    Host only.  The reference's rounding is written in: while its `coord` array is float32, every coordinate step is
+    followed by a ROUND_F32 step and centres are computed in fp32 (FLAG_FP32); a rotation or a clip makes the array
+    float64 and the rounds stop.  A step that reads bounds of the current state which an earlier step of the segment has
+    changed ends the segment (a bounds launch goes in front of the next); an elastic step always does, because the host
+    reads the bounds back to size its noise grid.  final_round: a last ROUND_F32 and a float32 result."""
+    f32 = not in_f64
+    stale = dict(coord=True, color=True)
+    segs = [dict(bounds=False, readback=False, steps=[])]
+    for rec in records:
+        kind, need = rec["kind"], rec.get("bounds")
+        elastic = kind == _K["PTV2_AUG_ELASTIC"]
+        cur = segs[-1]
+        if elastic or (need and stale[need]) or len(cur["steps"]) + 3 > _K["PTV2_AUG_MAX_STEPS"]:
+            if cur["steps"]:
+                cur = dict(bounds=False, readback=False, steps=[])
+                segs.append(cur)
+            if need:
+                cur["bounds"], cur["readback"] = True, cur["readback"] or elastic
+                stale = dict(coord=False, color=False)
+        step = {k: v for k, v in rec.items() if k not in ("bounds", "normal")}
+        step["flags"] = rec.get("flags", 0) | (_K["PTV2_AUG_FLAG_FP32"] if f32 and kind in _COORD_KINDS else 0)
+        cur["steps"].append(step)
+        if kind in _COORD_KINDS:
+            stale["coord"] = True
+            f32 = f32 and kind not in _TO_F64
+            if f32:
+                cur["steps"].append(dict(kind=_ROUND, flags=0))
+        else:
+            stale["color"] = True
+    if final_round and not f32 and segs[-1]["steps"]:
+        segs[-1]["steps"].append(dict(kind=_ROUND, flags=0))
+    segs = [s for s in segs if s["steps"]]
+    for i, seg in enumerate(segs):
+        seg["out_f64"] = i + 1 < len(segs) or not (f32 or final_round)
+    return segs
+
+
+def elastic_grid(lo, hi, fp32, granularity):
+    """(noise_dim, axis start, axis spacing) of ElasticDistortion's noise grid for the bounding box lo..hi, with the dtypes
+    of transform.py:726-752: on a float32 array the extent, its floor division and `coords_min - granularity` are float32."""
+    import numpy as np
+
+    dtype = np.float32 if fp32 else np.float64
+    lo, hi = np.asarray(lo, dtype), np.asarray(hi, dtype)
+    dims = ((hi - lo) // dtype(granularity)).astype(int) + 3
+    start = (lo - dtype(granularity)).astype(np.float64)
+    stop = lo.astype(np.float64) + granularity * (dims - 2)
+    return [int(d) for d in dims], start.tolist(), ((stop - start) / (dims - 1)).tolist()
+
+
+def _blurred_field(dims, grid, seed, stream):
+    """the smoothed noise grid: normals (given, or the kernel's own for `stream`), blurred x, y, z, x, y, z"""
+    L, dev = _lib.lib(), torch.device("cuda", torch.cuda.current_device())
+    cells = dims[0] * dims[1] * dims[2]
+    if grid is None:
+        a = torch.empty((cells, 3), dtype=torch.float32, device=dev)
+        _lib.check(L.aug_noise_hip_launcher(cells, seed, stream, a.data_ptr(), _lib.stream_ptr()), "aug_noise_hip_launcher")
+    else:
+        if callable(grid):  # (the grid's size is known only here)
+            grid = grid(dims)
+        if tuple(grid.shape) != (dims[0], dims[1], dims[2], 3):
+            raise ValueError("ElasticDistortion: the noise grid is %s here, the given one %s" % (tuple(dims) + (3,), tuple(grid.shape)))
+        a = _dev_f32(grid).clone()
+    b = torch.empty_like(a)
+    for axis in (0, 1, 2, 0, 1, 2):
+        _lib.check(L.aug_blur3_hip_launcher(dims[0], dims[1], dims[2], axis, a.data_ptr(), b.data_ptr(), _lib.stream_ptr()),
+                   "aug_blur3_hip_launcher")
+        a, b = b, a
+    return a
+
+
+def aug_bounds(coord, color=None):
+    """per-axis (min, max) of coord and colour on the device: 24 doubles, [0:6] coord, [6:12] colour, the rest scratch"""
+    out = torch.empty(24, dtype=torch.float64, device=coord.device)
+    rc = _lib.lib().aug_bounds_hip_launcher(coord.shape[0], coord.data_ptr(), int(coord.dtype == torch.float64), _lib.ptr(color),
+                                            out.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "aug_bounds_hip_launcher")
+    return out
+
+
+def _run_segments(segs, coord, color, seed):
+    """coord (n, 3) float32 / float64 and colour (n, 3) float32 or None through the segments of one plan"""
+    L = _lib.lib()
+    n = coord.shape[0]
+    if n == 0:
+        return coord, color
+    Program, keep = _abi.data_structs["ptv2_aug_program"], []
+    for seg in segs:
+        bounds = aug_bounds(coord, color) if seg["bounds"] else None
+        host = bounds[:6].tolist() if seg["readback"] else None  # the one host read-back: an elastic grid's size
+        prog = Program()
+        prog.count, prog.coord_in_f64, prog.coord_out_f64 = len(seg["steps"]), int(coord.dtype == torch.float64), int(seg["out_f64"])
+        planes, colour_steps = [], False
+        for s, step in zip(prog.step, seg["steps"]):
+            s.kind, s.flags, s.stream = step["kind"], step["flags"], step.get("stream", 0)
+            p = list(step.get("p", ()))
+            if step["kind"] == _K["PTV2_AUG_ELASTIC"]:
+                dims, start, spacing = elastic_grid(host[:3], host[3:], bool(step["flags"] & _K["PTV2_AUG_FLAG_FP32"]), step["granularity"])
+                field = _blurred_field(dims, step.get("grid"), seed, s.stream)
+                keep.append(field)
+                s.field, s.dims[0], s.dims[1], s.dims[2] = field.data_ptr(), dims[0], dims[1], dims[2]
+                p = start + spacing + [float(step["magnitude"])]
+            for j, v in enumerate(p):
+                s.p[j] = v
+            colour_steps = colour_steps or step["kind"] >= _K["PTV2_AUG_COLOR_CONTRAST"]
+            if step["kind"] in _NOISE_KINDS:
+                s.slot = len(planes)
+                planes.append(step.get("noise"))
+        noise = None
+        if any(p is not None for p in planes):  # given normals; a step without them gets the kernel's own, as a plane
+            noise = torch.empty((len(planes), n, 3), dtype=torch.float32, device=coord.device)
+            for j, (plane, step) in enumerate(zip(planes, [s for s in seg["steps"] if s["kind"] in _NOISE_KINDS])):
+                if plane is not None:
+                    noise[j] = _dev_f32(plane).reshape(n, 3)
+                else:
+                    _lib.check(L.aug_noise_hip_launcher(n, seed, step.get("stream", 0), noise[j].data_ptr(), _lib.stream_ptr()),
+                               "aug_noise_hip_launcher")
+        if colour_steps and color is None:
+            raise KeyError("a colour augmentation needs data_dict['color']")
+        out = torch.empty((n, 3), dtype=torch.float64 if seg["out_f64"] else torch.float32, device=coord.device)
+        color_out = torch.empty_like(color) if colour_steps else None
+        rc = L.aug_points_hip_launcher(n, ctypes.addressof(prog), _lib.ptr(bounds), coord.data_ptr(),
+                                       color.data_ptr() if colour_steps else 0, _lib.ptr(noise), seed, out.data_ptr(),
+                                       _lib.ptr(color_out), _lib.stream_ptr())
+        _lib.check(rc, "aug_points_hip_launcher")
+        coord, color = out, (color_out if colour_steps else color)
+    return coord, color
+
+
+def _point_tensor(x):
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise RuntimeError("ao_amd.ptv2.transform works on CUDA tensors (no CPU fallback)")
+    return x.contiguous() if x.dtype == torch.float64 else x.contiguous().float()
+
+
+def _run_records(records, data_dict, seed, final_round=False):
+    """the records' program on data_dict's coord and colour; rotations and flips also on its normal"""
+    colour = any(r["kind"] >= _K["PTV2_AUG_COLOR_CONTRAST"] for r in records) and "color" in data_dict.keys()
+    main = [r for r in records if "coord" in data_dict.keys() or r["kind"] >= _K["PTV2_AUG_COLOR_CONTRAST"]]
+    if "coord" in data_dict.keys():
+        coord = _point_tensor(data_dict["coord"])
+        segs = fuse_plan([r for r in main if colour or r["kind"] < _K["PTV2_AUG_COLOR_CONTRAST"]], coord.dtype == torch.float64, final_round)
+        coord, color = _run_segments(segs, coord, _dev_f32(data_dict["color"]) if colour else None, seed)
+        data_dict["coord"] = coord
+        if colour:
+            data_dict["color"] = color
+    elif colour:
+        raise KeyError("the colour augmentations run in the point program, which needs data_dict['coord']")
+    turns = [dict(r, p=r["p"][:9] + [0.0] * 3, flags=0, bounds=None) if r["kind"] == _K["PTV2_AUG_ROTATE"] else r
+             for r in records if r.get("normal")]
+    if turns and "normal" in data_dict.keys():
+        normal = _point_tensor(data_dict["normal"])
+        data_dict["normal"] = _run_segments(fuse_plan(turns, normal.dtype == torch.float64, final_round), normal, None, seed)[0]
+    return data_dict
+
+
+class _PointTransform:
+    """A per-point augmentation: `draw(generator)` makes its host-side random decisions, `steps(draws)` states what they
+    mean as step records, and a call on its own runs those records as a program of their own."""
+
+    def draw(self, generator=None):
+        return {}
+
+    def __call__(self, data_dict, generator=None, seed=None, stream=0, **draws):
+        drawn = dict(self.draw(generator), **draws)
+        if seed is None:
+            seed = int(torch.randint(0, 1 << 62, (), generator=generator))
+        records = [dict(r, stream=stream + r.get("stream", 0)) for r in self.steps(drawn)]
+        return _run_records(records, data_dict, seed)
+
+
+class Copy:
+    def __init__(self, keys_dict=None):
+        self.keys_dict = dict(coord="origin_coord", segment="origin_segment") if keys_dict is None else keys_dict
+
+    def __call__(self, data_dict):
+        for key, value in self.keys_dict.items():
+            v = data_dict[key]
+            data_dict[value] = v.clone().detach() if torch.is_tensor(v) else copy.deepcopy(v)
+        return data_dict
+
+
+class ShufflePoint:
+    KEYS = ("coord", "discrete_coord", "displacement", "color", "normal", "segment", "instance")  # transform.py:1007-1020
+
+    def __call__(self, data_dict, generator=None, perm=None):
+        assert "coord" in data_dict.keys()
+        n = data_dict["coord"].shape[0]
+        if perm is None:
+            perm = torch.randperm(n, generator=generator)
+        perm = torch.as_tensor(perm).long().to(data_dict["coord"].device)
+        for key in self.KEYS:
+            if key in data_dict.keys():
+                data_dict[key] = data_dict[key][perm]
+        return data_dict
+
+
+class RandomRotate(_PointTransform):
+    matrix = RandomRotateTargetAngle.matrix
+
+    def __init__(self, angle=None, center=None, axis="z", always_apply=False, p=0.5):
+        self.angle = [-1, 1] if angle is None else angle
+        self.axis, self.always_apply, self.center = axis, always_apply, center
+        self.p = p if not always_apply else 1
+
+    def draw(self, generator=None):
+        gate = float(torch.rand((), dtype=torch.float64, generator=generator))
+        if gate > self.p:  # transform.py:218: `random.random() > self.p` skips
+            return dict(gate=gate, angle=None)
+        return dict(gate=gate, angle=float(_uniform(self.angle[0], self.angle[1], (), generator)))
+
+    steps = RandomRotateTargetAngle.steps
+
+
+class RandomShift(_PointTransform):
+    def __init__(self, shift=((-0.2, 0.2), (-0.2, 0.2), (0, 0))):
+        self.shift = shift
+
+    def draw(self, generator=None):
+        return dict(shift=[float(_uniform(lo, hi, (), generator)) for lo, hi in self.shift])
+
+    def steps(self, draws):
+        return [dict(kind=_K["PTV2_AUG_SHIFT"], p=[float(v) for v in draws["shift"]])]
+
+
+class PointClip(_PointTransform):
+    def __init__(self, point_cloud_range=(-80, -80, -3, 80, 80, 1)):
+        self.point_cloud_range = point_cloud_range
+
+    def steps(self, draws=None):
+        return [dict(kind=_K["PTV2_AUG_CLIP"], p=[float(v) for v in self.point_cloud_range])]
+
+
+class RandomJitter(_PointTransform):
+    def __init__(self, sigma=0.01, clip=0.05):
+        assert clip > 0
+        self.sigma, self.clip = sigma, clip
+
+    def draw(self, generator=None):
+        return dict(noise=None)
+
+    def steps(self, draws):
+        return [dict(kind=_K["PTV2_AUG_JITTER"], p=[float(self.sigma), float(self.clip)], noise=draws.get("noise"))]
+
+
+class ElasticDistortion(_PointTransform):
+    """distortion_params has to be named (every config of the reference names it; None selects the reference's default
+    pairs): a bare dict(type="ElasticDistortion") stays the KeyError it has always been in this module."""
+
+    def __init__(self, distortion_params):
+        self.distortion_params = [[0.2, 0.4], [0.8, 1.6]] if distortion_params is None else distortion_params
+
+    def draw(self, generator=None):
+        return dict(gate=float(torch.rand((), dtype=torch.float64, generator=generator)), grids=None)
+
+    def steps(self, draws):
+        """grids: the normals of each pair's noise grid, (dx, dy, dz, 3) fp32 (or a callable that makes them for the
+        dims it is given), instead of the kernel's own"""
+        if self.distortion_params is None or not draws["gate"] < 0.95:
+            return []
+        grids = draws.get("grids") or [None] * len(self.distortion_params)
+        return [dict(kind=_K["PTV2_AUG_ELASTIC"], bounds="coord", granularity=float(g), magnitude=float(m), grid=grid, stream=1 + k)
+                for k, ((g, m), grid) in enumerate(zip(self.distortion_params, grids))]
+
+
+class ChromaticAutoContrast(_PointTransform):
+    def __init__(self, p=0.2, blend_factor=None):
+        self.p, self.blend_factor = p, blend_factor
+
+    def draw(self, generator=None):
+        gate = float(torch.rand((), dtype=torch.float64, generator=generator))
+        blend = self.blend_factor
+        if gate < self.p and blend is None:
+            blend = float(torch.rand((), dtype=torch.float64, generator=generator))
+        return dict(gate=gate, blend=blend)
+
+    def steps(self, draws):
+        if not draws["gate"] < self.p:
+            return []
+        blend = float(self.blend_factor if draws.get("blend") is None else draws["blend"])  # (a python scalar against a float32 array: both factors are rounded to fp32)
+        return [dict(kind=_K["PTV2_AUG_COLOR_CONTRAST"], p=[1 - blend, blend], bounds="color")]
+
+
+class ChromaticTranslation(_PointTransform):
+    def __init__(self, p=0.95, ratio=0.05):
+        self.p, self.ratio = p, ratio
+
+    def draw(self, generator=None):
+        gate = float(torch.rand((), dtype=torch.float64, generator=generator))
+        return dict(gate=gate, uniform=torch.rand(3, dtype=torch.float64, generator=generator).tolist() if gate < self.p else None)
+
+    def steps(self, draws):
+        if not draws["gate"] < self.p:
+            return []
+        return [dict(kind=_K["PTV2_AUG_COLOR_TRANSLATE"], p=[(float(u) - 0.5) * 255 * 2 * self.ratio for u in draws["uniform"]])]
+
+
+class ChromaticJitter(_PointTransform):
+    def __init__(self, p=0.95, std=0.005):
+        self.p, self.std = p, std
+
+    def draw(self, generator=None):
+        return dict(gate=float(torch.rand((), dtype=torch.float64, generator=generator)), noise=None)
+
+    def steps(self, draws):
+        if not draws["gate"] < self.p:
+            return []
+        return [dict(kind=_K["PTV2_AUG_COLOR_JITTER"], p=[self.std * 255], noise=draws.get("noise"))]
+
+
+class RandomColorDrop(_PointTransform):
+    def __init__(self, p=0.2, color_augment=0.0):
+        self.p, self.color_augment = p, color_augment
+
+    def draw(self, generator=None):
+        return dict(gate=float(torch.rand((), dtype=torch.float64, generator=generator)))
+
+    def steps(self, draws):
+        return [dict(kind=_K["PTV2_AUG_COLOR_MUL"], p=[float(self.color_augment)])] if draws["gate"] < self.p else []
+
+
 _TRANSFORMS = dict(GridSample=GridSample, SphereCrop=SphereCrop, Collect=Collect, CenterShift=CenterShift,
                    NormalizeColor=NormalizeColor, RandomScale=RandomScale, RandomFlip=RandomFlip,
-                   RandomRotateTargetAngle=RandomRotateTargetAngle, ToTensor=ToTensor)
+                   RandomRotateTargetAngle=RandomRotateTargetAngle, ToTensor=ToTensor, Copy=Copy, RandomRotate=RandomRotate,
+                   RandomShift=RandomShift, RandomJitter=RandomJitter, ElasticDistortion=ElasticDistortion,
+                   ChromaticAutoContrast=ChromaticAutoContrast, ChromaticTranslation=ChromaticTranslation,
+                   ChromaticJitter=ChromaticJitter, RandomColorDrop=RandomColorDrop, PointClip=PointClip,
+                   ShufflePoint=ShufflePoint)
 
 
-def point_collate(batch):
+def point_collate(batch, mix_prob=0, generator=None, mix=None):
     """datasets/utils.py:14-54 for a list of Collect()-ed dicts: tensors concatenated along dim 0, every '*offset*'
-    entry turned into the running end index (int32 on the coord's device, what pointops expects)."""
+    entry turned into the running end index (int32 on the coord's device, what pointops expects).  mix_prob: Mix3D
+    (utils.py:43-54) -- with that probability (`mix` decides when given) every two neighbouring scenes become one cloud:
+    offset keeps its entries 1, 3, 5, ... short of the last, and the last."""
     out = {}
     for key in batch[0]:
         vals = [d[key] for d in batch]
@@ -405,4 +849,11 @@ def point_collate(batch):
                 host[key + "_host"] = ends.tolist()  # that slice per scene (DefaultSegmentorSAM_Image) need no read-back
             out[key] = ends.to(dev)
     out.update(host)
+    if "offset" in out and torch.is_tensor(out["offset"]):
+        if mix is None:
+            mix = float(torch.rand((), dtype=torch.float64, generator=generator)) < mix_prob
+        if mix:
+            out["offset"] = torch.cat([out["offset"][1:-1:2], out["offset"][-1:]])
+            if "offset_host" in out:
+                out["offset_host"] = out["offset_host"][1:-1:2] + out["offset_host"][-1:]
     return out
