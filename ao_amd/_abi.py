@@ -114,3 +114,10 @@ if not os.path.exists(DATA_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % DATA_HEADER)
 with open(DATA_HEADER) as _f:
     data_consts, data_structs, data_signatures = parse(_f.read())
+
+# the third public header (REAL's epoch-end label refinement), likewise
+REFINE_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_refine_hip.h")
+if not os.path.exists(REFINE_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % REFINE_HEADER)
+with open(REFINE_HEADER) as _f:
+    refine_consts, refine_structs, refine_signatures = parse(_f.read())

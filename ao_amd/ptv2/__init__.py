@@ -17,3 +17,4 @@ from .segmentor import DefaultSegmentor, DefaultSegmentorSAM_Image, S3DIS_BACKBO
 from .losses import LovaszLoss, lovasz_softmax  # noqa: F401
 from .cac import CACSegmentor  # noqa: F401
 from .tester import SemSegTester, VoteTable, test_scene  # noqa: F401
+from .refine import LabelRefiner, grid_cells, grid_prompts, refine_scene, scene_confidence  # noqa: F401

@@ -17,7 +17,8 @@ when every staging slot is still in flight (back-pressure), or in `flush()` (epo
 basket).  Later writes win, in step order, exactly as the reference's sequential assignments do.
 
 With 288 GB of HBM the whole S3DIS basket (~272 rooms x ~1 M points x 13 floats = 14 GB) would also fit on the
-device; the host form is kept because the consumer (SAM prompting, voting, numpy) lives on the host.
+device; the host form is kept because a scene is read once per epoch: `ao_amd.ptv2.refine_scene` (refine.py, the device
+form of that epoch-end refinement) takes a basket entry as it is and uploads it once.
 """
 import queue
 import threading
