@@ -15,7 +15,7 @@
 // caller's grow-only workspace.
 #include <algorithm>
 
-#include "common.h"
+#include "dense_common.h"
 #include "gva_plan.h"
 
 namespace {
@@ -166,26 +166,34 @@ struct GemmRb16Scope {
 };
 }  // namespace
 
+// BatchNorm `i` of a Block as the record-fed launchers take it: the record buffer `part` (records of rb rows), where the
+// statistics and the folded affine go (the Saved carve), gamma / beta, and the running buffers -- here, and only here, NULL
+// unless the Block trains and has them
+static const int BN_GAMMA[PTV2_BLK_NBN] = {PTV2_BLK_N1_G, PTV2_BLK_QN_G, PTV2_BLK_KN_G, PTV2_BLK_PN_G,
+                                           PTV2_BLK_WN_G, PTV2_BLK_N2_G, PTV2_BLK_N3_G};  // (beta: the next parameter)
+static dense::BnTileSet bn_set(const ptv2_block *B, int i, const Saved &S, float *part, int rb) {
+    const bool track = B->training && B->run_mean[i] && B->run_var[i];
+    dense::BnTileSet T{};
+    T.part = part; T.rb = rb;
+    T.mean = S.mean[i]; T.rstd = S.rstd[i]; T.sc = S.bsc[i]; T.sh = S.bsh[i];
+    T.gamma = B->param[BN_GAMMA[i]]; T.beta = B->param[BN_GAMMA[i] + 1];
+    if (track) { T.run_mean = B->run_mean[i]; T.run_var = B->run_var[i]; T.batches = B->batches[i]; }
+    return T;
+}
+
 // statistics of BatchNorm `i` (input h, (n,c)) -> S.mean / S.rstd / S.sc / S.sh: from the producing GEMM's epilogue
-// records (`part` != NULL), from a pass over h (`part` == NULL, batch statistics), or from the running buffers (eval)
-static int bn_prepare(const ptv2_block *B, int i, const float *h, float *part, const float *gamma, const float *beta,
-                      const Saved &S, const Work &W, void *stream, int rb = 64) {
+// records (`part` != NULL, records of rb rows), from a pass over h (`part` == NULL, batch statistics), or from the running
+// buffers (eval)
+static int bn_prepare(const ptv2_block *B, int i, const float *h, float *part, const Saved &S, const Work &W, void *stream,
+                      int rb = 64) {
+    const dense::BnTileSet T = bn_set(B, i, S, part, rb);
     if (use_batch(B, i)) {
-        const bool track = B->training && B->run_mean[i] && B->run_var[i];
-        float *rm = track ? B->run_mean[i] : nullptr, *rv = track ? B->run_var[i] : nullptr;
-        long long *nb = track ? B->batches[i] : nullptr;
-        if (part && rb != 64)
-            return bn_tiles_finalize_rb(B->n, B->c, rb, part, gamma, beta, S.mean[i], S.rstd[i], S.bsc[i], S.bsh[i], rm, rv, nb, B->eps,
-                                        B->momentum, stream);
-        if (part)
-            return bn_tiles_finalize_hip_launcher(B->n, B->c, part, gamma, beta, S.mean[i], S.rstd[i], S.bsc[i], S.bsh[i], rm, rv,
-                                                  nb, B->eps, B->momentum, stream);
-        return bn_stats_affine_hip_launcher(B->n, B->c, h, gamma, beta, S.mean[i], S.rstd[i], S.bsc[i], S.bsh[i], rm, rv, nb, B->eps,
-                                            B->momentum, W.dense, W.dense_bytes, stream);
+        if (part) return bn_tiles_finalize_rb(B->n, B->c, T, B->eps, B->momentum, stream);
+        return bn_stats_affine_hip_launcher(B->n, B->c, h, T.gamma, T.beta, T.mean, T.rstd, T.sc, T.sh, T.run_mean, T.run_var, T.batches,
+                                            B->eps, B->momentum, W.dense, W.dense_bytes, stream);
     }
     hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(divup(B->c, 256)), dim3(256), 0, (hipStream_t)stream, B->c,
-                       (const float *)B->run_mean[i], (const float *)B->run_var[i], B->eps, gamma, beta, S.mean[i], S.rstd[i],
-                       S.bsc[i], S.bsh[i]);
+                       (const float *)B->run_mean[i], (const float *)B->run_var[i], B->eps, T.gamma, T.beta, T.mean, T.rstd, T.sc, T.sh);
     return PTV2_OK;
 }
 
@@ -223,7 +231,7 @@ extern "C" int ptv2_block_forward_hip_launcher(const ptv2_block *B, void *worksp
         float *ys[1] = {S.h1}, *sts[1] = {st_h1};
         RUN(rows_gemm_fused_hip_launcher(n, c, c, 1, 0, xs, ws, 0, nullptr, ys, 0, nullptr, nullptr, sts, stream));
     }
-    RUN(bn_prepare(B, 0, S.h1, st_h1, P[PTV2_BLK_N1_G], P[PTV2_BLK_N1_B], S, W, stream, rb));
+    RUN(bn_prepare(B, 0, S.h1, st_h1, S, W, stream, rb));
     // linear_q / linear_k / linear_v on f1 = ReLU(BN1(h1)) (applied on the operand load), statistics of hq, hk
     {
         const float *xs[3] = {S.h1, S.h1, S.h1}, *ws[3] = {P[PTV2_BLK_Q_W], P[PTV2_BLK_K_W], P[PTV2_BLK_V_W]};
@@ -232,17 +240,11 @@ extern "C" int ptv2_block_forward_hip_launcher(const ptv2_block *B, void *worksp
         RUN(rows_gemm_fused_hip_launcher(n, c, c, 3, 0, xs, ws, 0, bs, ys, 0, S.bsc[0], S.bsh[0], sts, stream));
     }
     if (st_hq && st_hk) {  // both from their GEMM records: one launch finishes the two BatchNorms
-        const bool tq = B->training && B->run_mean[1] && B->run_var[1], tk = B->training && B->run_mean[2] && B->run_var[2];
-        float *parts[2] = {st_hq, st_hk}, *means[2] = {S.mean[1], S.mean[2]}, *rstds[2] = {S.rstd[1], S.rstd[2]};
-        float *scs[2] = {S.bsc[1], S.bsc[2]}, *shs[2] = {S.bsh[1], S.bsh[2]};
-        const float *gs[2] = {P[PTV2_BLK_QN_G], P[PTV2_BLK_KN_G]}, *bs[2] = {P[PTV2_BLK_QN_B], P[PTV2_BLK_KN_B]};
-        float *rms[2] = {tq ? B->run_mean[1] : nullptr, tk ? B->run_mean[2] : nullptr};
-        float *rvs[2] = {tq ? B->run_var[1] : nullptr, tk ? B->run_var[2] : nullptr};
-        long long *nbs[2] = {tq ? B->batches[1] : nullptr, tk ? B->batches[2] : nullptr};
-        RUN(bn_tiles_finalize_pair(n, c, parts, gs, bs, means, rstds, scs, shs, rms, rvs, nbs, B->eps, B->momentum, stream, rb));
+        const dense::BnTileSet qk[2] = {bn_set(B, 1, S, st_hq, rb), bn_set(B, 2, S, st_hk, rb)};
+        RUN(bn_tiles_finalize_pair(n, c, qk, B->eps, B->momentum, stream));
     } else {
-        RUN(bn_prepare(B, 1, S.hq, st_hq, P[PTV2_BLK_QN_G], P[PTV2_BLK_QN_B], S, W, stream, rb));
-        RUN(bn_prepare(B, 2, S.hk, st_hk, P[PTV2_BLK_KN_G], P[PTV2_BLK_KN_B], S, W, stream, rb));
+        RUN(bn_prepare(B, 1, S.hq, st_hq, S, W, stream, rb));
+        RUN(bn_prepare(B, 2, S.hk, st_hk, S, W, stream, rb));
     }
     // grouped vector attention (q, k enter as hq, hk + folded affine)
     ptv2_gva_block V;
@@ -253,8 +255,7 @@ extern "C" int ptv2_block_forward_hip_launcher(const ptv2_block *B, void *worksp
     RUN(gva_block_forward_stats(&V, use_batch(B, 5) ? W.stat[0] : nullptr, &attn_stats, W.gva, W.gva_bytes, stream));
     // norm2 (statistics from those records, else by a pass over attn) -> fc3 on f2 = ReLU(BN2(attn)) (+ statistics of h3)
     // -> norm3 -> tail
-    RUN(bn_prepare(B, 5, S.attn, attn_stats ? W.stat[0] : nullptr, P[PTV2_BLK_N2_G], P[PTV2_BLK_N2_B], S, W, stream,
-                   attn_stats ? attn_stats : 64));
+    RUN(bn_prepare(B, 5, S.attn, attn_stats ? W.stat[0] : nullptr, S, W, stream, attn_stats ? attn_stats : 64));
     {
         const float *xs[1] = {S.attn}, *ws[1] = {P[PTV2_BLK_FC3_W]};
         float *ys[1] = {S.h3}, *sts[1] = {st_h3};
@@ -262,14 +263,10 @@ extern "C" int ptv2_block_forward_hip_launcher(const ptv2_block *B, void *worksp
     }
     // norm3 + tail: at the deep levels the apply kernel merges the tile records itself (one launch instead of two)
     int tail_done = 0;
-    if (st_h3) {
-        const bool track = B->training && B->run_mean[6] && B->run_var[6];
-        tail_done = bn_tiles_apply_residual(n, c, st_h3, P[PTV2_BLK_N3_G], P[PTV2_BLK_N3_B], S.mean[6], S.rstd[6], S.bsc[6], S.bsh[6],
-                                            track ? B->run_mean[6] : nullptr, track ? B->run_var[6] : nullptr,
-                                            track ? B->batches[6] : nullptr, B->eps, B->momentum, S.h3, B->x, B->rowscale, B->y, stream, rb);
-    }
+    if (st_h3)
+        tail_done = bn_tiles_apply_residual(n, c, bn_set(B, 6, S, st_h3, rb), B->eps, B->momentum, S.h3, B->x, B->rowscale, B->y, stream);
     if (!tail_done) {
-        RUN(bn_prepare(B, 6, S.h3, st_h3, P[PTV2_BLK_N3_G], P[PTV2_BLK_N3_B], S, W, stream, rb));
+        RUN(bn_prepare(B, 6, S.h3, st_h3, S, W, stream, rb));
         RUN(bn_apply_residual_hip_launcher(n, c, S.h3, S.mean[6], S.rstd[6], P[PTV2_BLK_N3_G], P[PTV2_BLK_N3_B], B->x, B->rowscale,
                                            B->y, stream));
     }

@@ -106,16 +106,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(
 
 // the same from the row GEMM's epilogue records part[nrb][2][c] (per 64-row block: column sums and sums of squares
 // about the block mean), merged with the parallel-variance identity  M2 = sum_b (M2_b + S_b^2 / n_b) - n mean^2
-// one or two tensors per launch (blockIdx.z selects the set: the q / k BatchNorms of a Block are finished together)
-struct BnTileSet {
-    const float *part;
-    float *mean, *rstd, *run_mean, *run_var;
-    long long *batches;
-    const float *gamma, *beta;
-    float *sc, *sh;
-    double *fold;  // two-level scratch (bn_fold_tiles_kernel)
-    int rb;        // rows per record: 64 (the row GEMM's epilogue, the projection kernels) or 16 (gva_fwd_tile.hip); 0 = 64
-};
+// one or two BnTileSet (dense_common.h) per launch (blockIdx.z selects the set: the q / k BatchNorms of a Block are finished together)
 __device__ __forceinline__ int bn_tile_rows(const BnTileSet &S, int k, int n) {  // rows of record k
     const int rb = S.rb ? S.rb : 64;
     return (n - k * rb) < rb ? (n - k * rb) : rb;
@@ -814,36 +805,28 @@ extern "C" int bn_tiles_finalize_hip_launcher(int n, int c, float *part, const f
     return bn_tiles_finalize_sets(n, c, 1, &S, eps, momentum, stream);
 }
 // internal (block.hip): records of rb rows each (bn_tiles_floats_rb floats) -- the attention's tile kernel leaves 16-row records
-int bn_tiles_finalize_rb(int n, int c, int rb, float *part, const float *gamma, const float *beta, float *mean, float *rstd, float *sc,
-                         float *sh, float *running_mean, float *running_var, long long *num_batches_tracked, float eps, float momentum,
-                         void *stream) {
+int bn_tiles_finalize_rb(int n, int c, const BnTileSet &set, float eps, float momentum, void *stream) {
+    const int rb = set.rb;
     if (n < 1 || c < 4 || (rb != 16 && rb != 64)) return PTV2_ERR_ARG;
-    BnTileSet S{part, mean, rstd, running_mean, running_var, num_batches_tracked, gamma, beta, sc, sh, nullptr, rb};
+    BnTileSet S = set;
     return bn_tiles_finalize_sets(n, c, 1, &S, eps, momentum, stream, rb);
 }
 
-// two tensors of one shape (internal to the block runtime: the q / k BatchNorms); arrays of 2
-int bn_tiles_finalize_pair(int n, int c, float *const *part, const float *const *gamma, const float *const *beta,
-                           float *const *mean, float *const *rstd, float *const *sc, float *const *sh, float *const *running_mean,
-                           float *const *running_var, long long *const *num_batches_tracked, float eps, float momentum,
-                           void *stream, int rb) {
+// two tensors of one shape (internal to the block runtime: the q / k BatchNorms), records of sets[0].rb rows
+int bn_tiles_finalize_pair(int n, int c, const BnTileSet (&sets)[2], float eps, float momentum, void *stream) {
+    const int rb = sets[0].rb;
     if (n < 1 || c < 4 || (rb != 16 && rb != 64)) return PTV2_ERR_ARG;
-    BnTileSet S[2];
-    for (int i = 0; i < 2; ++i)
-        S[i] = BnTileSet{part[i], mean[i], rstd[i], running_mean[i], running_var[i], num_batches_tracked[i], gamma[i], beta[i], sc[i],
-                         sh[i], nullptr, rb};
+    BnTileSet S[2] = {sets[0], sets[1]};
     return bn_tiles_finalize_sets(n, c, 2, S, eps, momentum, stream, rb);
 }
 
 // internal (block.hip): BatchNorm statistics from the producing GEMM's tile records AND the Block tail
 // y = ReLU(residual + rowscale * BN(x)) in one launch when the records are few (deep levels); returns 0 when it declines
-int bn_tiles_apply_residual(int n, int c, float *part, const float *gamma, const float *beta, float *mean, float *rstd, float *sc,
-                            float *sh, float *running_mean, float *running_var, long long *num_batches_tracked, float eps,
-                            float momentum, const float *x, const float *residual, const float *rowscale, float *y, void *stream,
-                            int rb) {
+int bn_tiles_apply_residual(int n, int c, const BnTileSet &S, float eps, float momentum, const float *x, const float *residual,
+                            const float *rowscale, float *y, void *stream) {
+    const int rb = S.rb;
     const int nrb = (n + rb - 1) / rb;
     if (nrb > (rb == 16 ? 512 : 256) || c % 4 != 0 || bn_finapply_off() || (rb != 16 && rb != 64)) return 0;
-    BnTileSet S{part, mean, rstd, running_mean, running_var, num_batches_tracked, gamma, beta, sc, sh, nullptr, rb};
     const dim3 grid((unsigned)((c + FA_COLS - 1) / FA_COLS), (unsigned)((n + FA_ROWS - 1) / FA_ROWS));
     {
         PtvScopedTimer t(KID_BN_APPLY, (hipStream_t)stream, 12.0 * n * c);
@@ -855,12 +838,11 @@ int bn_tiles_apply_residual(int n, int c, float *part, const float *gamma, const
 
 // internal (model.hip): the same for y = ReLU(BN(x)) -- statistics from the producing GEMM's 64-row records and the apply pass in
 // one launch (was bn_stats + bn_finalize + bn_apply); returns 0 when it declines (many records: the three launches stay)
-int bn_tiles_apply_relu(int n, int c, float *part, const float *gamma, const float *beta, float *mean, float *rstd, float *running_mean,
-                        float *running_var, long long *num_batches_tracked, float eps, float momentum, const float *x, float *y,
-                        void *stream) {
+int bn_tiles_apply_relu(int n, int c, const BnTileSet &set, float eps, float momentum, const float *x, float *y, void *stream) {
     const int nrb = (n + 63) / 64;
     if (nrb > 512 || c % 4 != 0 || bn_finapply_off()) return 0;
-    BnTileSet S{part, mean, rstd, running_mean, running_var, num_batches_tracked, gamma, beta, nullptr, nullptr, nullptr, 64};
+    BnTileSet S = set;  // (no folded affine asked for; 64-row records)
+    S.sc = S.sh = nullptr; S.rb = 64;
     const dim3 grid((unsigned)((c + FA_COLS - 1) / FA_COLS), (unsigned)((n + FA_ROWS - 1) / FA_ROWS));
     {
         PtvScopedTimer t(KID_BN_APPLY, (hipStream_t)stream, 8.0 * n * c);

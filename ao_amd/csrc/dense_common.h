@@ -20,4 +20,18 @@ static inline int bn_grid(int n, int c) {
     return (int)std::max<long long>(1, std::min<long long>(b, n <= 16384 ? 128 : MAX_BLK));
 }
 
+
+// One BatchNorm fed from the statistics records its producing launch left in part[nrb][2][c] (per block of rb rows: column sums
+// and sums of squares about the block mean): what the finalize writes (mean / rstd; the running buffers, NULL: not tracked; the
+// folded affine sc / sh, NULL: not asked for) and gamma / beta.  A kernel argument of bn.hip: the layout is fixed.
+struct BnTileSet {
+    const float *part;
+    float *mean, *rstd, *run_mean, *run_var;
+    long long *batches;
+    const float *gamma, *beta;
+    float *sc, *sh;
+    double *fold;  // two-level scratch (bn_fold_tiles_kernel)
+    int rb;        // rows per record: 64 (the row GEMM's epilogue, the projection kernels) or 16 (gva_fwd_tile.hip); 0 = 64
+};
+
 }  // namespace dense

@@ -472,14 +472,13 @@ __global__ __launch_bounds__(TPB) void aggregate_bwd_gv_kernel(int n, int k, int
     }
 }
 
-static void launch_bwd_gv(hipStream_t st, int n, int k, int c, int g, const float *w, const float *g_out, const int *inv_ptr,
-                          const int *inv_rows, float *gv) {
+static void launch_bwd_gv(hipStream_t st, int n, int k, int c, int g, const AttnBwdIn &X, float *gv) {
     const int I = c / g;
     const int V = I >= 4 ? 4 : I;
     const int main_blocks = (int)std::min<long long>(((long long)n * (c / V) + TPB - 1) / TPB, MAX_BLOCKS * 4);
     const PtvRiders Rs = ptv2_rider_take();  // gv depends on none of the parameter-gradient sums queued before this launch
     const dim3 grid((unsigned)(main_blocks + rider_blocks(Rs)));
-#define GVCASE(II) case II: hipLaunchKernelGGL(aggregate_bwd_gv_kernel<II>, grid, dim3(TPB), 0, st, n, k, c, g, w, g_out, inv_ptr, inv_rows, gv, main_blocks, Rs); break;
+#define GVCASE(II) case II: hipLaunchKernelGGL(aggregate_bwd_gv_kernel<II>, grid, dim3(TPB), 0, st, n, k, c, g, X.w, X.g_out, X.inv_ptr, X.inv_rows, gv, main_blocks, Rs); break;
     switch (I) { GVCASE(1) GVCASE(2) GVCASE(4) GVCASE(8) GVCASE(16) GVCASE(32) GVCASE(64) default: break; }
 #undef GVCASE
 }
@@ -519,13 +518,14 @@ extern "C" int gva_aggregate_forward_hip_launcher(int n, int k, int c, int g, co
                                                   const float *sh, const float *Ww2, const float *bw2, const float *v,
                                                   const float *a, const float *b, const float *coord, const int *idx,
                                                   float *out_v, float *A, float *sw, float *w, void *stream) {
-    return gva_aggregate_forward(gva_plan(n, k, c, g, ptv2_attn_drop_current().thresh != 0, true), n, k, c, g, W1, sc, sh, Ww2, bw2, v,
-                                 a, b, coord, idx, out_v, A, sw, w, stream);
+    AttnIn I{};
+    I.W1 = W1; I.sc = sc; I.sh = sh; I.Ww2 = Ww2; I.bw2 = bw2; I.v = v; I.a = a; I.b = b; I.coord = coord; I.idx = idx;
+    AttnFwdOut O{};
+    O.out_v = out_v; O.A = A; O.sw = sw; O.w = w;
+    return gva_aggregate_forward(gva_plan(n, k, c, g, ptv2_attn_drop_current().thresh != 0, true), n, k, c, g, I, O, stream);
 }
 
-int gva_aggregate_forward(const GvaPlan &P, int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
-                          const float *Ww2, const float *bw2, const float *v, const float *a, const float *b, const float *coord,
-                          const int *idx, float *out_v, float *A, float *sw, float *w, void *stream) {
+int gva_aggregate_forward(const GvaPlan &P, int n, int k, int c, int g, const AttnIn &I, const AttnFwdOut &O, void *stream) {
     if (n < 0 || !pow2(k) || k > 64 || c < 1 || g < 1 || c % g != 0) return PTV2_ERR_ARG;
     if (n == 0) return PTV2_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -534,17 +534,13 @@ int gva_aggregate_forward(const GvaPlan &P, int n, int k, int c, int g, const fl
     {
         PtvScopedTimer t(KID_SOFTMAX_ROWS, st, 4.0 * ((double)rows * (2 * g + 1) + (double)n * g));
         if (P.softmax == GvaPlan::SM_POINT) {
-            const int rc = gva_softmax_point_launch(n, k, g, W1, sc, sh, Ww2, bw2, idx, w, sw, st, ptv2_attn_drop_current());
+            const int rc = gva_softmax_point_launch(n, k, g, I, O, st, ptv2_attn_drop_current());
             if (rc != PTV2_OK) return rc;
         } else {
             const PtvDrop drop = ptv2_attn_drop_current();
-#define CALL(GG)                                                                                                                  \
-    if (drop.thresh)                                                                                                              \
-        hipLaunchKernelGGL((softmax_rows_kernel<GG, true>), dim3(nb_rows), dim3(TPB), 0, st, rows, k, W1, sc, sh, Ww2, bw2, idx, w, \
-                           sw, drop);                                                                                             \
-    else                                                                                                                          \
-        hipLaunchKernelGGL((softmax_rows_kernel<GG, false>), dim3(nb_rows), dim3(TPB), 0, st, rows, k, W1, sc, sh, Ww2, bw2, idx, \
-                           w, sw, drop)
+#define CALL(GG)                                                                                                      \
+    auto kern = drop.thresh ? softmax_rows_kernel<GG, true> : softmax_rows_kernel<GG, false>;                         \
+    hipLaunchKernelGGL(kern, dim3(nb_rows), dim3(TPB), 0, st, rows, k, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.idx, O.w, O.sw, drop)
             GVA_DISPATCH_G(g, CALL)
 #undef CALL
         }
@@ -555,8 +551,8 @@ int gva_aggregate_forward(const GvaPlan &P, int n, int k, int c, int g, const fl
         // w + idx + coord in; v rows (each unique row once); out_v and A out
         PtvScopedTimer t(KID_AGG_TILE, st, 4.0 * ((double)rows * (g + 1) + (double)n * (3 + 2 * c) + (double)n * g * c));
 #define CALL(GG)                                                                                                       \
-    hipLaunchKernelGGL(aggregate_tile_kernel<GG>, dim3((n + tp - 1) / tp), dim3(TPB), lds, st, n, k, c, tp, (const float *)w, \
-                       v, a, b, coord, idx, out_v, A)
+    hipLaunchKernelGGL(aggregate_tile_kernel<GG>, dim3((n + tp - 1) / tp), dim3(TPB), lds, st, n, k, c, tp, (const float *)O.w, \
+                       I.v, I.a, I.b, I.coord, I.idx, O.out_v, O.A)
         GVA_DISPATCH_G(g, CALL)
 #undef CALL
     }
@@ -564,16 +560,12 @@ int gva_aggregate_forward(const GvaPlan &P, int n, int k, int c, int g, const fl
     return PTV2_OK;
 }
 
-// Either g_A / g_sw are handed in (behind a peb_bwd launch), or -- for the forms the plan marks fused_peb, which do the backward
-// of the grouped projection themselves and never materialise g_A (N,G,C) / g_sw -- Wp2 / bp2 and the inverse table
-int gva_aggregate_backward(const GvaPlan &P, int n, int k, int c, int g, const float *W1, const float *sc, const float *sh,
-                                   const float *Ww2, const float *bw2, const float *v, const float *a, const float *b,
-                                   const float *coord, const int *idx, const float *w, const float *g_out, const float *g_A,
-                                   const float *g_sw, const float *g_fused_Wp2, const float *g_fused_bp2, const int *inv_ptr,
-                                   const int *inv_rows, float *gW1, float *gsc, float *gsh, float *gWw2, float *gbw2, float *gv,
-                                   float *ga, float *gb, void *workspace, size_t workspace_bytes, void *stream) {
-    if (g_A ? !g_sw : (!P.fused_peb || !inv_ptr || !g_fused_Wp2 || !g_fused_bp2)) return PTV2_ERR_ARG;
-    const GvaPlan::BwdAgg form = g_A ? P.bwd_agg_given_gA : P.bwd_agg;
+// Either X.g_A / X.g_sw are handed in (behind a peb_bwd launch), or -- for the forms the plan marks fused_peb, which do the backward
+// of the grouped projection themselves and never materialise g_A (N,G,C) / g_sw -- I.Wp2 / I.bp2 and the inverse table
+int gva_aggregate_backward(const GvaPlan &P, int n, int k, int c, int g, const AttnIn &I, const AttnBwdIn &X, const AttnBwdOut &O,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    if (X.g_A ? !X.g_sw : (!P.fused_peb || !X.inv_ptr || !I.Wp2 || !I.bp2)) return PTV2_ERR_ARG;
+    const GvaPlan::BwdAgg form = X.g_A ? P.bwd_agg_given_gA : P.bwd_agg;
     if (n < 0 || !pow2(k) || k > 64 || c < 1 || g < 1 || c % g != 0 || !pow2(c / g) || c / g > 64) return PTV2_ERR_ARG;
     if (!workspace || workspace_bytes < agg_workspace_bytes(P, n, k, c, g)) return PTV2_ERR_WORKSPACE;
     if (n == 0) return PTV2_OK;
@@ -591,13 +583,12 @@ int gva_aggregate_backward(const GvaPlan &P, int n, int k, int c, int g, const f
             PtvScopedTimer t(KID_BWD_TILE_K + P.g_slot - 1, st,  // (+ 0..3 for G = 12, 24, 48, 64)
                              4.0 * ((double)rows * (2 * g + 1) + (double)n * (3 + 2 * c)));
             const PtvDeferScope defer;  // its record sums ride on the gv launch below (which needs none of them)
-            const int rc = gva_bwd_tile_launch(n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, g_fused_Wp2, g_fused_bp2, gW1,
-                                               gsc, gsh, gWw2, gbw2, ga, gb, part, part_bytes / sizeof(float), ptv2_attn_drop_current(), st);
+            const int rc = gva_bwd_tile_launch(n, k, c, g, I, X, O, part, part_bytes / sizeof(float), ptv2_attn_drop_current(), st);
             if (rc != PTV2_OK) return rc;
         }
         {
             PtvScopedTimer t(KID_BWD_GV, st, 4.0 * ((double)rows * (g + 1) + 2.0 * n * c + n));
-            launch_bwd_gv(st, n, k, c, g, w, g_out, inv_ptr, inv_rows, gv);
+            launch_bwd_gv(st, n, k, c, g, X, O.gv);
         }
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
@@ -609,14 +600,12 @@ int gva_aggregate_backward(const GvaPlan &P, int n, int k, int c, int g, const f
             // W1, idx, coord, g_out, g_sw, v rows (unique once), g_A in; gW1 out
             PtvScopedTimer t(KID_BWD_POINT + P.g_slot, st, 4.0 * ((double)rows * (2 * g + 1) + (double)n * (3 + 2 * c + g) + (double)n * g * c));
             const PtvDeferScope defer;  // its record sums ride on the gv launch below (which needs none of them)
-            const int rc = gva_bwd_point_launch(n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, g_A, g_sw, gW1, gsc,
-                                                gsh, gWw2, gbw2, ga, gb, part, part_bytes / sizeof(float), st, g_fused_Wp2,
-                                                g_fused_bp2, ptv2_attn_drop_current());
+            const int rc = gva_bwd_point_launch(n, k, c, g, I, X, O, part, part_bytes / sizeof(float), st, ptv2_attn_drop_current());
             if (rc != PTV2_OK) return rc;
         }
         {
             PtvScopedTimer t(KID_BWD_GV, st, 4.0 * ((double)rows * (g + 1) + 2.0 * n * c + n));
-            launch_bwd_gv(st, n, k, c, g, w, g_out, inv_ptr, inv_rows, gv);
+            launch_bwd_gv(st, n, k, c, g, X, O.gv);
         }
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
@@ -640,33 +629,33 @@ int gva_aggregate_backward(const GvaPlan &P, int n, int k, int c, int g, const f
     if (lds_tile > 32 * 1024)                                                                                           \
         (void)hipFuncSetAttribute((const void *)aggregate_bwd_tile_kernel<GG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                   (int)lds_tile);                                                                       \
-    hipLaunchKernelGGL(aggregate_bwd_tile_kernel<GG>, dim3(nb_tile), dim3(WAVE), lds_tile, st, n, k, c, w, v, a, b, coord, idx, \
-                       g_out, g_A, g_sw, gw, inv_ptr ? (float *)nullptr : gv, part)
+    hipLaunchKernelGGL(aggregate_bwd_tile_kernel<GG>, dim3(nb_tile), dim3(WAVE), lds_tile, st, n, k, c, X.w, I.v, I.a, I.b, I.coord, \
+                       I.idx, X.g_out, X.g_A, X.g_sw, gw, X.inv_ptr ? (float *)nullptr : O.gv, part)
     {
         // w, idx, coord, g_out, g_sw, v rows (unique once), g_A in; grad w out
         PtvScopedTimer t(KID_BWD_TILE, st, 4.0 * ((double)rows * (2 * g + 1) + (double)n * (3 + 2 * c + g) + (double)n * g * c));
         GVA_DISPATCH_G(g, CALL)
     }
 #undef CALL
-    launch_finalize(st, (const float *)part, nb_tile, 4 * c, MapAB{ga, gb});
-    if (inv_ptr)
+    launch_finalize(st, (const float *)part, nb_tile, 4 * c, MapAB{O.ga, O.gb});
+    if (X.inv_ptr)
     {
         PtvScopedTimer t(KID_BWD_GV, st, 4.0 * ((double)rows * (g + 1) + 2.0 * n * c + n));
-        launch_bwd_gv(st, n, k, c, g, w, g_out, inv_ptr, inv_rows, gv);
+        launch_bwd_gv(st, n, k, c, g, X, O.gv);
     }
     const int nb_rows = (int)std::min<long long>((rows + TPB - 1) / TPB, MAX_BLOCKS);
 #define CALL(GG)                                                                                                      \
-    hipLaunchKernelGGL(aggregate_bwd_rows_kernel<GG>, dim3(nb_rows), dim3(TPB), 0, st, rows, k, W1, sc, sh, Ww2, bw2, idx, \
-                       (const float *)gw, gW1, gz, yb, part)
+    hipLaunchKernelGGL(aggregate_bwd_rows_kernel<GG>, dim3(nb_rows), dim3(TPB), 0, st, rows, k, I.W1, I.sc, I.sh, I.Ww2, I.bw2, \
+                       I.idx, (const float *)gw, O.gW1, gz, yb, part)
     {
         PtvScopedTimer t(KID_BWD_ROWS, st, 4.0 * (double)rows * (5 * g + 1));
         GVA_DISPATCH_G(g, CALL)
     }
 #undef CALL
-    launch_finalize(st, (const float *)part, nb_rows, 2 * g, MapSplit2<float>{gsc, gsh, g});
+    launch_finalize(st, (const float *)part, nb_rows, 2 * g, MapSplit2<float>{O.gsc, O.gsh, g});
     PTV2_CHECK_LAUNCH();
     // grad Ww2[g][g'] = sum_rows gz[r,g] y[r,g'],  grad bw2 = column sums of gz: the Linear weight-gradient reduction
-    return linear_wgrad_hip_launcher((int)rows, g, g, gz, yb, gWw2, gbw2, dense_ws, dense_bytes, stream);
+    return linear_wgrad_hip_launcher((int)rows, g, g, gz, yb, O.gWw2, O.gbw2, dense_ws, dense_bytes, stream);
 }
 
 // backward of gva_attention_forward_hip_launcher: the grouped projection's backward folded in
@@ -679,8 +668,14 @@ extern "C" int gva_attention_backward_hip_launcher(int n, int k, int c, int g, c
                                                    void *stream) {
     const GvaPlan P = gva_plan(n, k, c, g, ptv2_attn_drop_current().thresh != 0, inv_ptr != nullptr);
     if (!P.bwd_tile_shape) return PTV2_ERR_ARG;
-    return gva_aggregate_backward(P, n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, w, g_out, nullptr, nullptr, Wp2, bp2,
-                                  inv_ptr, inv_rows, gW1, gsc, gsh, gWw2, gbw2, gv, ga, gb, workspace, workspace_bytes, stream);
+    AttnIn I{};
+    I.W1 = W1; I.sc = sc; I.sh = sh; I.Ww2 = Ww2; I.bw2 = bw2; I.v = v; I.a = a; I.b = b; I.coord = coord; I.idx = idx;
+    I.Wp2 = Wp2; I.bp2 = bp2;
+    AttnBwdIn X{};
+    X.w = w; X.g_out = g_out; X.inv_ptr = inv_ptr; X.inv_rows = inv_rows;
+    AttnBwdOut O{};
+    O.gW1 = gW1; O.gsc = gsc; O.gsh = gsh; O.gWw2 = gWw2; O.gbw2 = gbw2; O.gv = gv; O.ga = ga; O.gb = gb;
+    return gva_aggregate_backward(P, n, k, c, g, I, X, O, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gva_aggregate_backward_hip_launcher(int n, int k, int c, int g, const float *W1, const float *sc,
@@ -692,7 +687,12 @@ extern "C" int gva_aggregate_backward_hip_launcher(int n, int k, int c, int g, c
                                                    float *gsh, float *gWw2, float *gbw2, float *gv, float *ga,
                                                    float *gb, void *workspace, size_t workspace_bytes, void *stream) {
     if (!g_A || !g_sw) return PTV2_ERR_ARG;
-    return gva_aggregate_backward(gva_plan(n, k, c, g, ptv2_attn_drop_current().thresh != 0, inv_ptr != nullptr), n, k, c, g, W1, sc,
-                                  sh, Ww2, bw2, v, a, b, coord, idx, w, g_out, g_A, g_sw, nullptr, nullptr, inv_ptr, inv_rows, gW1,
-                                  gsc, gsh, gWw2, gbw2, gv, ga, gb, workspace, workspace_bytes, stream);
+    AttnIn I{};
+    I.W1 = W1; I.sc = sc; I.sh = sh; I.Ww2 = Ww2; I.bw2 = bw2; I.v = v; I.a = a; I.b = b; I.coord = coord; I.idx = idx;
+    AttnBwdIn X{};
+    X.w = w; X.g_out = g_out; X.g_A = g_A; X.g_sw = g_sw; X.inv_ptr = inv_ptr; X.inv_rows = inv_rows;
+    AttnBwdOut O{};
+    O.gW1 = gW1; O.gsc = gsc; O.gsh = gsh; O.gWw2 = gWw2; O.gbw2 = gbw2; O.gv = gv; O.ga = ga; O.gb = gb;
+    return gva_aggregate_backward(gva_plan(n, k, c, g, ptv2_attn_drop_current().thresh != 0, inv_ptr != nullptr), n, k, c, g, I, X, O,
+                                  workspace, workspace_bytes, stream);
 }

@@ -336,6 +336,44 @@ static FoldPFwdArgs fold_p_args(const ptv2_gva_block *B) {
                         B->training, (double)B->n * B->k, B->eps_p, B->momentum_p, B->a, B->b, B->rstd_p};
 }
 
+// the operand bundles of the stage launchers (gva_common.h), filled once per direction from B / G / the workspace carve
+static AttnIn attn_in(const ptv2_gva_block *B, bool with_proj) {  // with_proj: Wp2 / bp2 for the forms that fold the projection in
+    AttnIn I{};
+    I.W1 = B->W1; I.sc = B->sc; I.sh = B->sh; I.Ww2 = B->Ww2; I.bw2 = B->bw2; I.v = B->v; I.a = B->a; I.b = B->b; I.coord = B->coord;
+    I.idx = B->idx; I.Wp2 = with_proj ? B->Wp2 : nullptr; I.bp2 = with_proj ? B->bp2 : nullptr;
+    return I;
+}
+static LogitsIn logits_in(const ptv2_gva_block *B) {
+    LogitsIn I{};
+    I.kW = B->kW; I.qW = B->qW; I.a = B->a; I.b = B->b; I.M = B->M; I.cW = B->cW; I.coord = B->coord; I.idx = B->idx;
+    return I;
+}
+static AttnFwdOut attn_fwd_out(const ptv2_gva_block *B, const BlockWs &W, float *out_stats) {
+    AttnFwdOut O{};
+    O.w = B->w; O.sw = B->sw; O.A = B->A; O.out_v = W.out_v; O.out = B->out; O.stats = out_stats;
+    return O;
+}
+static AttnBwdIn attn_bwd_in(const ptv2_gva_block *B, const ptv2_gva_block_grads *G, const BlockWs &W) {
+    AttnBwdIn X{};  // (W.gA / W.g_sw are NULL exactly when the plan says fused_peb: the form then works from Wp2 / bp2)
+    X.w = B->w; X.sw = B->sw; X.g_out = G->g_out; X.g_A = W.gA; X.g_sw = W.g_sw; X.inv_ptr = G->inv_ptr; X.inv_rows = G->inv_rows;
+    return X;
+}
+static AttnBwdOut attn_bwd_out(const ptv2_gva_block_grads *G, const BlockWs &W) {
+    AttnBwdOut O{};
+    O.gW1 = W.gW1; O.gsc = W.gsc; O.gsh = W.gsh; O.gWw2 = G->gWw2; O.gbw2 = G->gbw2; O.gv = G->gv; O.ga = W.ga2; O.gb = W.gb2;
+    return O;
+}
+static LogitsBwdIn logits_bwd_in(const ptv2_gva_block *B, const ptv2_gva_block_grads *G, const BlockWs &W) {
+    LogitsBwdIn X{};  // (gT1 / gT2 stay NULL: FoldWBwdArgs derives them)
+    X.W1 = B->W1; X.gW1 = W.gW1; X.inv_ptr = G->inv_ptr; X.inv_rows = G->inv_rows;
+    return X;
+}
+static LogitsBwdOut logits_bwd_out(const BlockWs &W) {
+    LogitsBwdOut O{};
+    O.gkW = W.gkW; O.gqW = W.gqW; O.ga = W.ga1; O.gb = W.gb1; O.gM = W.gM; O.gcW = W.gcW;
+    return O;
+}
+
 int gva_fold_forward_batched(int count, const ptv2_gva_block *blocks, void *stream) {
     for (int i0 = 0; i0 < count; i0 += 8) {
         FoldFwdBatch batch{};
@@ -390,26 +428,26 @@ int gva_block_forward_stats(const ptv2_gva_block *B, float *out_stats, int *stat
         RUN(skinny_linear_forward_pair(n, c, g, xs, B->Ww1, xsc, xsh, ys, stream));
     }
     // logits + their BatchNorm statistics; the final reduction of the sums also folds BN_w into (sc, sh)
-    RUN(gva_logits_forward_fold(P, n, k, c, g, B->kW, B->qW, B->a, B->b, B->M, B->cW, B->coord, B->idx, B->W1, W.T1, W.T2,
+    RUN(gva_logits_forward_fold(P, n, k, c, g, logits_in(B), LogitsOut{B->W1, W.T1, W.T2},
                                 FoldWFwdArgs{B->gamma_w, B->beta_w, B->run_mean_w, B->run_var_w, B->batches_w, B->training, rows,
                                              B->eps_w, B->momentum_w, B->sc, B->sh, B->mean_w, B->rstd_w},
                                 W.stage, W.stage_bytes, stream));
     // softmax, aggregation and the grouped projection
+    const AttnIn I = attn_in(B, true);
+    AttnFwdOut O = attn_fwd_out(B, W, out_stats);
     switch (P.fwd) {
     case GvaPlan::F_POINT:  // one launch at the full-resolution level (gva_fwd_point.hip)
-        RUN(gva_fwd_point_launch(n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, B->Wp2, B->bp2,
-                                 B->w, B->sw, B->A, B->out, out_stats, stream));
+        RUN(gva_fwd_point_launch(n, k, c, g, I, O, stream));
         if (out_stats && stats_done) *stats_done = 64;
         break;
     case GvaPlan::F_TILE:  // the deep levels: one launch per 16-point tile x group block (gva_fwd_tile.hip); no out_v, no A
-        RUN(gva_fwd_tile_launch(n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, B->Wp2, B->bp2,
-                                B->w, B->sw, B->out, out_stats, P.keeps_A ? B->A : nullptr, stream));
+        if (!P.keeps_A) O.A = nullptr;
+        RUN(gva_fwd_tile_launch(n, k, c, g, I, O, stream));
         if (out_stats && stats_done) *stats_done = 16;
         break;
     case GvaPlan::F_STAGED:  // three launches
-        RUN(gva_aggregate_forward(P, n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, W.out_v,
-                                  B->A, B->sw, B->w, stream));
-        RUN(gva_peb_forward_stats(n, c, g, B->A, B->Wp2, B->bp2, B->sw, W.out_v, B->out, out_stats, stats_done, stream));
+        RUN(gva_aggregate_forward(P, n, k, c, g, I, O, stream));
+        RUN(gva_peb_forward_stats(n, c, g, I, O, stats_done, stream));
         break;
     }
     PTV2_CHECK_LAUNCH();
@@ -448,6 +486,8 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
     const double rows = (double)n * k;
     const int I = c / g;
     PtvRiderGuard riders;  // an error return below must not leave queued sums (pointers into this call's workspace) behind
+    const AttnIn In = attn_in(B, P.fused_peb);
+    const AttnBwdIn X = attn_bwd_in(B, G, W);
     // 1. projection after the neighbour sum: g_A, g_sw (formed inside the point kernel for the narrow instances),
     //    grad Wp2 (direct part), grad bp2 (direct part)
     if (P.fused_peb && !G->inv_ptr) return PTV2_ERR_ARG;  // (the fused forms gather grad v through the inverse neighbour table)
@@ -460,8 +500,7 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
         // of its own per Block, bp2_grad_kernel: 15 x 6 us); where the weight gradient cannot (bf16 operands), the kernel below
         const PtvDeferScope defer;
         if (P.wp2_recompute) {  // A = w^T P is formed again inside the weight gradient (gva_wgrad_tile.hip)
-            RUN(gva_wp2_wgrad_recompute(n, k, c, g, G->g_out, B->w, B->sw, B->a, B->b, B->coord, B->idx, G->gWp2, G->gbp2, W.wp2_part,
-                                        W.wp2_bytes, stream));
+            RUN(gva_wp2_wgrad_recompute(n, k, c, g, In, X, G->gWp2, G->gbp2, W.wp2_part, W.wp2_bytes, stream));
             bp2_done = 1;
         } else
         RUN(linear_wgrad_strided_rowscale(n, I, c, g, G->g_out, c, I, B->A, (long long)g * c, c, G->gWp2, G->gbp2, B->sw, g, &bp2_done,
@@ -479,19 +518,16 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
         if (!own_final) launch_finalize(st, (const float *)W.part, nblk, c, MapVec<float>{G->gbp2});
     }
     // 2. softmax / aggregation stage
-    // (W.gA / W.g_sw are NULL exactly when the plan says fused_peb: the form then works from Wp2 / bp2)
-    RUN(gva_aggregate_backward(P, n, k, c, g, B->W1, B->sc, B->sh, B->Ww2, B->bw2, B->v, B->a, B->b, B->coord, B->idx, B->w, G->g_out,
-                               W.gA, W.g_sw, P.fused_peb ? B->Wp2 : nullptr, P.fused_peb ? B->bp2 : nullptr, G->inv_ptr, G->inv_rows,
-                               W.gW1, W.gsc, W.gsh, G->gWw2, G->gbw2, G->gv, W.ga2, W.gb2, W.stage, W.stage_bytes, stream));
+    RUN(gva_aggregate_backward(P, n, k, c, g, In, X, attn_bwd_out(G, W), W.stage, W.stage_bytes, stream));
     // 3. + 4. BatchNorm over the logits (its backward is evaluated in the prologue of the rows kernel), logits stage
     if (!G->inv_ptr) (void)ptv2_zero_async(W.gkW, sizeof(float) * (size_t)n * g, st);
     // the parameter-gradient sums of this stage and of the kW / qW weight gradient ride on the skinny_bwd launch below
     {
     const PtvDeferScope defer;
-    RUN(gva_logits_backward_foldw(P, n, k, c, g, B->a, B->b, B->M, B->coord, B->idx, B->W1, W.gW1, nullptr, nullptr,
+    RUN(gva_logits_backward_foldw(P, n, k, c, g, logits_in(B), logits_bwd_in(B, G, W),
                                   FoldWBwdArgs{B->gamma_w, B->mean_w, B->rstd_w, B->training, rows, W.gsc, W.gsh, G->ggamma_w,
                                                G->gbeta_w},
-                                  G->inv_ptr, G->inv_rows, W.gkW, W.gqW, W.ga1, W.gb1, W.gM, W.gcW, W.stage, W.stage_bytes, stream));
+                                  logits_bwd_out(W), W.stage, W.stage_bytes, stream));
     // 6. projections kW = k Ww1^T, qW = q Ww1^T: weight gradient first (its records in a region of their own), then the
     //    input gradients -- the launch that carries the queued sums
     {

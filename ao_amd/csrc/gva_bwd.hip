@@ -258,16 +258,18 @@ extern "C" int gva_logits_backward_hip_launcher(int n, int k, int c, int g, cons
                                                 const double *gT2, const int *inv_ptr, const int *inv_rows,
                                                 float *gkW, float *gqW, float *ga, float *gb, float *gM, float *gcW,
                                                 void *workspace, size_t workspace_bytes, void *stream) {
-    return gva_logits_backward_foldw(gva_plan(n, k, c, g, false, inv_ptr != nullptr), n, k, c, g, a, b, M, coord, idx, W1, gW1, gT1,
-                                     gT2, gva::FoldWBwdArgs{}, inv_ptr, inv_rows, gkW,
-                                     gqW, ga, gb, gM, gcW, workspace, workspace_bytes, stream);
+    LogitsIn I{};
+    I.a = a; I.b = b; I.M = M; I.coord = coord; I.idx = idx;
+    LogitsBwdIn X{};
+    X.W1 = W1; X.gW1 = gW1; X.gT1 = gT1; X.gT2 = gT2; X.inv_ptr = inv_ptr; X.inv_rows = inv_rows;
+    LogitsBwdOut O{};
+    O.gkW = gkW; O.gqW = gqW; O.ga = ga; O.gb = gb; O.gM = gM; O.gcW = gcW;
+    return gva_logits_backward_foldw(gva_plan(n, k, c, g, false, inv_ptr != nullptr), n, k, c, g, I, X, FoldWBwdArgs{}, O, workspace,
+                                     workspace_bytes, stream);
 }
 
-int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, const float *a, const float *b, const float *M,
-                              const float *coord,
-                              const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
-                              const gva::FoldWBwdArgs &F, const int *inv_ptr, const int *inv_rows, float *gkW, float *gqW, float *ga,
-                              float *gb, float *gM, float *gcW, void *workspace, size_t workspace_bytes, void *stream) {
+int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, const LogitsIn &I, const LogitsBwdIn &X,
+                              const FoldWBwdArgs &F, const LogitsBwdOut &O, void *workspace, size_t workspace_bytes, void *stream) {
     if (n < 0 || k < 1 || c < 1 || g < 1) return PTV2_ERR_ARG;
     if (!workspace || workspace_bytes < gva_workspace_bytes(n, k, c, g)) return PTV2_ERR_WORKSPACE;
     if (n == 0) return PTV2_OK;
@@ -281,14 +283,13 @@ int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, cons
             // W1, gW1 in, gWt out, idx, coord; parameter-sized outputs
             PtvScopedTimer t(KID_LOGITS_BWD_FUSED + P.g_slot, st,
                              4.0 * ((double)rows * (3 * g + 1) + 3.0 * n));
-            const int rc = gva_logits_bwd_fused_launch(n, k, c, g, a, b, M, coord, idx, W1, gW1, gT1, gT2, F, gWt, part,
-                                                       part_floats(c, g), gM, ga, gb, gcW, st);
+            const int rc = gva_logits_bwd_fused_launch(n, k, c, g, I, X, F, gWt, part, part_floats(c, g), O, st);
             if (rc != PTV2_OK) return rc;
         }
         {
             PtvScopedTimer t(KID_LOGITS_BWD_GATHER, st, 4.0 * ((double)rows * g + 2.0 * n * g + rows));
             hipLaunchKernelGGL(logits_bwd_gather_kernel, dim3(stage_grid((long long)n * g, TPB)), dim3(TPB), 0, st, n, k, g,
-                               (const float *)gWt, idx, inv_ptr, inv_rows, gkW, gqW);
+                               (const float *)gWt, I.idx, X.inv_ptr, X.inv_rows, O.gkW, O.gqW);
         }
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
@@ -297,16 +298,16 @@ int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, cons
     // arrive then had to sum (83-88 % of the wave cycles parked; 13.45 -> 13.35 ms per step with a quarter of the grid)
     const int nb_rows = stage_grid(rows * g / 64, TPB);
 #define CALL(GG) \
-    hipLaunchKernelGGL(logits_bwd_rows_kernel<GG>, dim3(nb_rows), dim3(TPB), 0, st, rows, W1, gW1, gT1, gT2, gWt, part, \
-                       cnt ? cnt + CNT_LOGITS_BWD_ROWS : nullptr, gcW, F)
+    hipLaunchKernelGGL(logits_bwd_rows_kernel<GG>, dim3(nb_rows), dim3(TPB), 0, st, rows, X.W1, X.gW1, X.gT1, X.gT2, gWt, \
+                       part, cnt ? cnt + CNT_LOGITS_BWD_ROWS : nullptr, O.gcW, F)
     const bool own_final = (size_t)nb_rows * g <= FUSED_FINAL_MAX;
     unsigned *cnt = own_final ? ptv2_stream_counters(st) : nullptr;
     if (own_final && !cnt) return PTV2_ERR_LAUNCH;
     GVA_DISPATCH_G(g, CALL)
 #undef CALL
-    if (!own_final) launch_finalize(st, (const float *)part, nb_rows, g, MapVec<float>{gcW});
+    if (!own_final) launch_finalize(st, (const float *)part, nb_rows, g, MapVec<float>{O.gcW});
     hipLaunchKernelGGL(logits_bwd_gather_kernel, dim3(stage_grid((long long)n * g, TPB)), dim3(TPB), 0, st, n, k, g,
-                       (const float *)gWt, idx, inv_ptr, inv_rows, gkW, gqW);
+                       (const float *)gWt, I.idx, X.inv_ptr, X.inv_rows, O.gkW, O.gqW);
     // params kernel: its partials go after the rows-kernel partials (still inside the partial region)
     float *ppart = part + (size_t)nb_rows * g;
     const int cbk = c < TPB ? c : TPB, nsl = c < TPB ? TPB / c : 1;
@@ -317,10 +318,10 @@ int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, cons
         int nb = 0;
         {
             PtvScopedTimer t(KID_LOGITS_BWD_PARAMS, st, 4.0 * ((double)rows * (g + 1) + 3.0 * n));
-            const int rc = gva_logits_params_point_launch(n, k, c, g, a, b, M, coord, idx, gWt, ppart, par_cap, &nb, st);
+            const int rc = gva_logits_params_point_launch(n, k, c, g, I, gWt, ppart, par_cap, &nb, st);
             if (rc != PTV2_OK) return rc;
         }
-        launch_finalize(st, (const float *)ppart, nb, c * (g + 4), MapLogitsParams{gM, ga, gb, g});
+        launch_finalize(st, (const float *)ppart, nb, c * (g + 4), MapLogitsParams{O.gM, O.ga, O.gb, g});
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
     }
@@ -329,15 +330,15 @@ int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, cons
     if (comb_bytes > 32 * 1024)                                                                                    \
         (void)hipFuncSetAttribute((const void *)logits_bwd_params_kernel<GG>,                                      \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)comb_bytes);                    \
-    hipLaunchKernelGGL(logits_bwd_params_kernel<GG>, dim3(nb_par), dim3(TPB), comb_bytes, st, n, k, c, a, b, M, coord, idx, \
-                       (const float *)gWt, ppart)
+    hipLaunchKernelGGL(logits_bwd_params_kernel<GG>, dim3(nb_par), dim3(TPB), comb_bytes, st, n, k, c, I.a, I.b, I.M, I.coord, \
+                       I.idx, (const float *)gWt, ppart)
     {
         const int passes = (c + TPB - 1) / TPB;  // the row stream is re-read once per 256-channel pass
         PtvScopedTimer t(KID_LOGITS_BWD_PARAMS, st, 4.0 * passes * ((double)rows * (g + 1) + 3.0 * n));
         GVA_DISPATCH_G(g, CALL)
     }
 #undef CALL
-    launch_finalize(st, (const float *)ppart, nb_par, c * (g + 4), MapLogitsParams{gM, ga, gb, g});
+    launch_finalize(st, (const float *)ppart, nb_par, c * (g + 4), MapLogitsParams{O.gM, O.ga, O.gb, g});
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
 }

@@ -297,10 +297,8 @@ __global__ __launch_bounds__(256) void logits_bwd_fused_kernel(int n, int k, con
 }
 
 template <int G, int C, int NW>
-int launch_logits_bwd_fused(int n, int k, const float *a, const float *b, const float *M, const float *coord, const int *idx,
-                            const float *W1, const float *gW1, const double *gT1, const double *gT2, const FoldWBwdArgs &F,
-                            float *gWt, float *part, size_t part_floats_avail, float *gM, float *ga, float *gb, float *gcW,
-                            hipStream_t st) {
+int launch_logits_bwd_fused(int n, int k, const LogitsIn &I, const LogitsBwdIn &X, const FoldWBwdArgs &F, float *gWt, float *part,
+                            size_t part_floats_avail, const LogitsBwdOut &O, hipStream_t st) {
     using K = LogitsBwdCfg<G, C, NW>;
     const size_t lds = sizeof(float4) * (C + 4 * 2 * 16) + sizeof(float) * (2 * K::GT * 16 + (K::PW > 1 ? K::REC : 0));
     auto kern = logits_bwd_fused_kernel<G, C, NW>;
@@ -317,8 +315,8 @@ int launch_logits_bwd_fused(int n, int k, const float *a, const float *b, const 
     long long cap = std::min<long long>(resident, (long long)(part_floats_avail / K::REC));
     if (cap < 1) return PTV2_ERR_WORKSPACE;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(groups, cap));
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, a, b, M, coord, idx, W1, gW1, gT1, gT2, gWt, part, F);
-    launch_finalize(st, (const float *)part, nblk, (int)K::REC, MapLogitsFused{gM, ga, gb, gcW, G, C});
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, I.a, I.b, I.M, I.coord, I.idx, X.W1, X.gW1, X.gT1, X.gT2, gWt, part, F);
+    launch_finalize(st, (const float *)part, nblk, (int)K::REC, MapLogitsFused{O.gM, O.ga, O.gb, O.gcW, G, C});
     return PTV2_OK;
 }
 
@@ -512,10 +510,8 @@ __global__ __launch_bounds__(256) void logits_bwd_fused6_kernel(int n, const flo
 }
 
 template <int C>
-int launch_logits_bwd_fused6(int n, const float *a, const float *b, const float *M, const float *coord, const int *idx,
-                             const float *W1, const float *gW1, const double *gT1, const double *gT2, const FoldWBwdArgs &F,
-                             float *gWt, float *part, size_t part_floats_avail, float *gM, float *ga, float *gb, float *gcW,
-                             hipStream_t st) {
+int launch_logits_bwd_fused6(int n, const LogitsIn &I, const LogitsBwdIn &X, const FoldWBwdArgs &F, float *gWt, float *part,
+                             size_t part_floats_avail, const LogitsBwdOut &O, hipStream_t st) {
     constexpr int REC = C * 10 + 16;
     const size_t lds = sizeof(float4) * (C + 4 * 2 * 16) + sizeof(float) * (2 * 16 + 4 * 96 + REC);
     auto kern = logits_bwd_fused6_kernel<C>;
@@ -530,8 +526,8 @@ int launch_logits_bwd_fused6(int n, const float *a, const float *b, const float 
     long long cap = std::min<long long>(resident, (long long)(part_floats_avail / REC));
     if (cap < 1) return PTV2_ERR_WORKSPACE;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(groups, cap));
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, a, b, M, coord, idx, W1, gW1, gT1, gT2, gWt, part, F);
-    launch_finalize(st, (const float *)part, nblk, REC, MapLogitsFused{gM, ga, gb, gcW, 6, C});
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, I.a, I.b, I.M, I.coord, I.idx, X.W1, X.gW1, X.gT1, X.gT2, gWt, part, F);
+    launch_finalize(st, (const float *)part, nblk, REC, MapLogitsFused{O.gM, O.ga, O.gb, O.gcW, 6, C});
     return PTV2_OK;
 }
 
@@ -548,18 +544,15 @@ int gva_logits_bwd_fused_supported(int k, int c, int g) {
     return (g == 12 && c == 96) || (g == 24 && c == 192) || (g == 48 && c == 384);
 }
 
-int gva_logits_bwd_fused_launch(int n, int k, int c, int g, const float *a, const float *b, const float *M, const float *coord,
-                                const int *idx, const float *W1, const float *gW1, const double *gT1, const double *gT2,
-                                const gva::FoldWBwdArgs &F, float *gWt, float *part, size_t part_floats_avail, float *gM, float *ga,
-                                float *gb, float *gcW, hipStream_t st) {
+int gva_logits_bwd_fused_launch(int n, int k, int c, int g, const gva::LogitsIn &I, const gva::LogitsBwdIn &X,
+                                const gva::FoldWBwdArgs &F, float *gWt, float *part, size_t part_floats_avail,
+                                const gva::LogitsBwdOut &O, hipStream_t st) {
     using namespace gva;
-#define ARGS n, k, a, b, M, coord, idx, W1, gW1, gT1, gT2, F, gWt, part, part_floats_avail, gM, ga, gb, gcW, st
-    if (g == 6 && c == 48)
-        return launch_logits_bwd_fused6<48>(n, a, b, M, coord, idx, W1, gW1, gT1, gT2, F, gWt, part, part_floats_avail, gM, ga, gb, gcW, st);
-    if (g == 12 && c == 96) return launch_logits_bwd_fused<12, 96, 1>(ARGS);
-    if (g == 24 && c == 192) return launch_logits_bwd_fused<24, 192, 4>(ARGS);  // (2 waves per point: 306 registers, 1 wave / SIMD)
-    if (g == 48 && c == 384) return launch_logits_bwd_fused<48, 384, 4>(ARGS);
-#undef ARGS
+    if (g == 6 && c == 48) return launch_logits_bwd_fused6<48>(n, I, X, F, gWt, part, part_floats_avail, O, st);
+    if (g == 12 && c == 96) return launch_logits_bwd_fused<12, 96, 1>(n, k, I, X, F, gWt, part, part_floats_avail, O, st);
+    if (g == 24 && c == 192)  // (2 waves per point: 306 registers, 1 wave / SIMD)
+        return launch_logits_bwd_fused<24, 192, 4>(n, k, I, X, F, gWt, part, part_floats_avail, O, st);
+    if (g == 48 && c == 384) return launch_logits_bwd_fused<48, 384, 4>(n, k, I, X, F, gWt, part, part_floats_avail, O, st);
     return PTV2_ERR_ARG;
 }
 
@@ -743,9 +736,7 @@ __global__ __launch_bounds__(256) void logits_fwd_mfma_kernel(int n, int k, cons
 }
 
 template <int G, int C, int NW>
-int launch_logits_fwd_mfma(int n, int k, const float *kW, const float *qW, const float *a, const float *b, const float *M,
-                           const float *cW, const float *coord, const int *idx, float *W1, float *part, double *T1, double *T2,
-                           const FoldWFwdArgs &F, hipStream_t st) {
+int launch_logits_fwd_mfma(int n, int k, const LogitsIn &I, const LogitsOut &O, float *part, const FoldWFwdArgs &F, hipStream_t st) {
     constexpr int GT = (G + 15) / 16, PW = 4 / NW;
     const size_t lds = sizeof(float4) * (C + 4 * 2 * 16) + sizeof(int) * 4 * 2 * 16 +
                        (NW > 1 ? sizeof(float) * (size_t)PW * NW * GT * 4 * 64 : 0);
@@ -763,11 +754,11 @@ int launch_logits_fwd_mfma(int n, int k, const float *kW, const float *qW, const
     const bool own_final = (size_t)nblk * 2 * G <= FUSED_FINAL_MAX;
     unsigned *cnt = own_final ? ptv2_stream_counters(st) : nullptr;
     if (own_final && !cnt) return PTV2_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, kW, qW, a, b, M, cW, coord, idx, W1, part,
-                       cnt ? cnt + CNT_LOGITS_FWD : nullptr, T1, T2, F);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, I.kW, I.qW, I.a, I.b, I.M, I.cW, I.coord, I.idx, O.W1, part,
+                       cnt ? cnt + CNT_LOGITS_FWD : nullptr, O.T1, O.T2, F);
     if (!own_final)
         hipLaunchKernelGGL(finalize_logit_sums_kernel, dim3((G + FLS_GROUPS - 1) / FLS_GROUPS), dim3(1024), 0, st, (const float *)part,
-                           nblk, G, T1, T2, F);
+                           nblk, G, O.T1, O.T2, F);
     return PTV2_OK;
 }
 
@@ -781,14 +772,11 @@ int gva_logits_fwd_mfma_supported(int k, int c, int g) {
 }
 
 // part: >= MAX_BLOCKS * 2 g floats
-int gva_logits_fwd_mfma_launch(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
-                               const float *M, const float *cW, const float *coord, const int *idx, float *W1, float *part,
-                               double *T1, double *T2, const gva::FoldWFwdArgs &F, hipStream_t st) {
+int gva_logits_fwd_mfma_launch(int n, int k, int c, int g, const gva::LogitsIn &I, const gva::LogitsOut &O, float *part,
+                               const gva::FoldWFwdArgs &F, hipStream_t st) {
     using namespace gva;
-#define ARGS n, k, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st
-    if (g == 12 && c == 96) return launch_logits_fwd_mfma<12, 96, 1>(ARGS);
-    if (g == 24 && c == 192) return launch_logits_fwd_mfma<24, 192, 1>(ARGS);
-    if (g == 48 && c == 384) return launch_logits_fwd_mfma<48, 384, 4>(ARGS);
-#undef ARGS
+    if (g == 12 && c == 96) return launch_logits_fwd_mfma<12, 96, 1>(n, k, I, O, part, F, st);
+    if (g == 24 && c == 192) return launch_logits_fwd_mfma<24, 192, 1>(n, k, I, O, part, F, st);
+    if (g == 48 && c == 384) return launch_logits_fwd_mfma<48, 384, 4>(n, k, I, O, part, F, st);
     return PTV2_ERR_ARG;
 }

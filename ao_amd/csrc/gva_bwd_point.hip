@@ -1101,28 +1101,24 @@ __global__ __launch_bounds__(256) void logits_params_point_kernel(int n, int k, 
 }
 
 template <int G, int C, int NW>
-int launch_params_point(int n, int k, const float *a, const float *b, const float *M, const float *coord, const int *idx,
-                        const float *gWt, float *part, int max_blocks, int *nblk_out, hipStream_t st) {
+int launch_params_point(int n, int k, const LogitsIn &I, const float *gWt, float *part, int max_blocks, int *nblk_out, hipStream_t st) {
     constexpr int PW = 4 / NW;
     const size_t lds = sizeof(float4) * (C + PW * 16) + (PW > 1 ? sizeof(float) * (size_t)C * (G + 4) : 0);
     const long long groups = ((long long)n + PW - 1) / PW;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(groups, max_blocks));
     auto kern = logits_params_point_kernel<G, C, NW>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, a, b, M, coord, idx, gWt, part);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, I.a, I.b, I.M, I.coord, I.idx, gWt, part);
     *nblk_out = nblk;
     return PTV2_OK;
 }
 
 template <int G, int C, int NW>
-int launch_bwd_point(int n, int k, const float *W1, const float *sc, const float *sh, const float *Ww2, const float *bw2,
-                     const float *v, const float *a, const float *b, const float *coord, const int *idx, const float *g_out,
-                     const float *g_A, const float *g_sw, float *gW1, float *gsc, float *gsh, float *gWw2, float *gbw2,
-                     float *ga, float *gb, float *part, size_t part_floats_avail, hipStream_t st, const float *Wp2,
-                     const float *bp2, PtvDrop drop) {
+int launch_bwd_point(int n, int k, const AttnIn &I, const AttnBwdIn &X, const AttnBwdOut &O, float *part, size_t part_floats_avail,
+                     hipStream_t st, PtvDrop drop) {
     using K = BwdPointCfg<G, C, NW>;
     constexpr bool HAS_LOCAL = G == 6 && C == 48 && NW == 1;  // the one instance where it pays (gva_bwd_point_local)
-    const bool local = Wp2 != nullptr;
+    const bool local = I.Wp2 != nullptr;
     if (local && !HAS_LOCAL) return PTV2_ERR_ARG;
     const size_t lds = sizeof(float) * (K::lds_floats + (local ? (size_t)C * C + C + 4 * (size_t)K::G16 * C + 4 * K::G16 : 0));
     // grid: exactly the workgroups that are resident at once (occupancy x CUs, at most 512).  Every workgroup stages
@@ -1146,33 +1142,30 @@ int launch_bwd_point(int n, int k, const float *W1, const float *sc, const float
     const int nblk = (int)std::max<long long>(1, std::min<long long>(groups, cap));
     const size_t dump_at = ((size_t)nblk * K::PF + 3) & ~(size_t)3;  // 16 dump rows of G16 floats behind the records
     if (dump_at + 16 * K::G16 > part_floats_avail) return PTV2_ERR_WORKSPACE;
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, g_A, g_sw,
-                       gW1, part, local ? Wp2 : (const float *)nullptr, local ? bp2 : (const float *)nullptr, drop, part + dump_at);
-    launch_finalize(st, (const float *)part, nblk, K::PF, MapBwdPoint{ga, gb, gsc, gsh, gWw2, gbw2, C, G});
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.v, I.a, I.b, I.coord, I.idx, X.g_out,
+                       X.g_A, X.g_sw, O.gW1, part, local ? I.Wp2 : (const float *)nullptr, local ? I.bp2 : (const float *)nullptr, drop,
+                       part + dump_at);
+    launch_finalize(st, (const float *)part, nblk, K::PF, MapBwdPoint{O.ga, O.gb, O.gsc, O.gsh, O.gWw2, O.gbw2, C, G});
     return PTV2_OK;
 }
 
 }  // namespace gva
 
 // parameter gradients of the logits stage on the matrix cores; writes nblk records of c (g + 4) floats to part
-int gva_logits_params_point_launch(int n, int k, int c, int g, const float *a, const float *b, const float *M,
-                                   const float *coord, const int *idx, const float *gWt, float *part, int max_blocks,
-                                   int *nblk_out, hipStream_t st) {
+int gva_logits_params_point_launch(int n, int k, int c, int g, const gva::LogitsIn &I, const float *gWt, float *part,
+                                   int max_blocks, int *nblk_out, hipStream_t st) {
     using namespace gva;
-#define ARGS n, k, a, b, M, coord, idx, gWt, part, max_blocks, nblk_out, st
-    if (g == 6 && c == 48) return launch_params_point<6, 48, 1>(ARGS);
-    if (g == 12 && c == 96) return launch_params_point<12, 96, 1>(ARGS);
-    if (g == 24 && c == 192) return launch_params_point<24, 192, 2>(ARGS);
-    if (g == 48 && c == 384) return launch_params_point<48, 384, 4>(ARGS);
-    if (g == 64 && c == 512) return launch_params_point<64, 512, 4>(ARGS);
-#undef ARGS
+    if (g == 6 && c == 48) return launch_params_point<6, 48, 1>(n, k, I, gWt, part, max_blocks, nblk_out, st);
+    if (g == 12 && c == 96) return launch_params_point<12, 96, 1>(n, k, I, gWt, part, max_blocks, nblk_out, st);
+    if (g == 24 && c == 192) return launch_params_point<24, 192, 2>(n, k, I, gWt, part, max_blocks, nblk_out, st);
+    if (g == 48 && c == 384) return launch_params_point<48, 384, 4>(n, k, I, gWt, part, max_blocks, nblk_out, st);
+    if (g == 64 && c == 512) return launch_params_point<64, 512, 4>(n, k, I, gWt, part, max_blocks, nblk_out, st);
     return PTV2_ERR_ARG;
 }
 
 // logits stage on the matrix cores; part: >= nblk * 2g floats; returns the grid size through *nblk_out
-int gva_logits_point_launch(int n, int k, int c, int g, const float *kW, const float *qW, const float *a, const float *b,
-                            const float *M, const float *cW, const float *coord, const int *idx, float *W1, float *part,
-                            double *T1, double *T2, const gva::FoldWFwdArgs &F, hipStream_t st) {
+int gva_logits_point_launch(int n, int k, int c, int g, const gva::LogitsIn &I, const gva::LogitsOut &O, float *part,
+                            const gva::FoldWFwdArgs &F, hipStream_t st) {
     using namespace gva;
     if (k < 1 || k > 16 || c % 4 != 0 || c > 2048) return PTV2_ERR_ARG;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(((long long)n + 3) / 4, MAX_BLOCKS));
@@ -1183,33 +1176,29 @@ int gva_logits_point_launch(int n, int k, int c, int g, const float *kW, const f
     switch (g) {
 #define CASE(GG)                                                                                                        \
     case GG:                                                                                                            \
-        hipLaunchKernelGGL(attention_logits_point_kernel<GG>, dim3(nblk), dim3(256), lds, st, n, k, c, kW, qW, a, b, M, cW, \
-                           coord, idx, W1, part, cnt ? cnt + CNT_LOGITS_FWD : nullptr, T1, T2, F);                     \
+        hipLaunchKernelGGL(attention_logits_point_kernel<GG>, dim3(nblk), dim3(256), lds, st, n, k, c, I.kW, I.qW, I.a, I.b, I.M, \
+                           I.cW, I.coord, I.idx, O.W1, part, cnt ? cnt + CNT_LOGITS_FWD : nullptr, O.T1, O.T2, F);      \
         break;
         CASE(6) CASE(12) CASE(24) CASE(48) CASE(64)
 #undef CASE
         default: return PTV2_ERR_ARG;
     }
-    if (!own_final) hipLaunchKernelGGL(finalize_logit_sums_kernel, dim3((g + FLS_GROUPS - 1) / FLS_GROUPS), dim3(1024), 0, st, (const float *)part, nblk, g, T1, T2, F);
+    if (!own_final) hipLaunchKernelGGL(finalize_logit_sums_kernel, dim3((g + FLS_GROUPS - 1) / FLS_GROUPS), dim3(1024), 0, st, (const float *)part, nblk, g, O.T1, O.T2, F);
     return PTV2_OK;
 }
 
 // forward softmax stage on the matrix cores (k <= 16; g one of the instantiated group counts)
-int gva_softmax_point_launch(int n, int k, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                             const float *bw2, const int *idx, float *w, float *sw, hipStream_t st, gva::PtvDrop drop) {
+int gva_softmax_point_launch(int n, int k, int g, const gva::AttnIn &I, const gva::AttnFwdOut &O, hipStream_t st,
+                             gva::PtvDrop drop) {
     using namespace gva;
     if (k < 1 || k > 16) return PTV2_ERR_ARG;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(((long long)n + 3) / 4, 256 * 8));
     switch (g) {
-#define CASE(GG)                                                                                                          \
-    case GG:                                                                                                              \
-        if (drop.thresh)                                                                                                  \
-            hipLaunchKernelGGL((attention_softmax_point_kernel<GG, true>), dim3(nblk), dim3(256), 0, st, n, k, W1, sc, sh, Ww2,  \
-                               bw2, idx, w, sw, drop);                                                                    \
-        else                                                                                                              \
-            hipLaunchKernelGGL((attention_softmax_point_kernel<GG, false>), dim3(nblk), dim3(256), 0, st, n, k, W1, sc, sh, Ww2, \
-                               bw2, idx, w, sw, drop);                                                                    \
-        break;
+#define CASE(GG)                                                                                                               \
+    case GG: {                                                                                                                 \
+        auto kern = drop.thresh ? attention_softmax_point_kernel<GG, true> : attention_softmax_point_kernel<GG, false>;        \
+        hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), 0, st, n, k, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.idx, O.w, O.sw, drop);  \
+    } break;
         CASE(6) CASE(12) CASE(24) CASE(48) CASE(64)
 #undef CASE
         default: return PTV2_ERR_ARG;
@@ -1234,19 +1223,14 @@ size_t gva_bwd_point_part_floats(int c, int g) {
     return std::max<size_t>((8u << 20) / sizeof(float), 512 * pf) + 1024;
 }
 
-int gva_bwd_point_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                         const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
-                         const float *g_out, const float *g_A, const float *g_sw, float *gW1, float *gsc, float *gsh,
-                         float *gWw2, float *gbw2, float *ga, float *gb, float *part, size_t part_floats_avail,
-                         hipStream_t st, const float *Wp2, const float *bp2, gva::PtvDrop drop) {
+int gva_bwd_point_launch(int n, int k, int c, int g, const gva::AttnIn &I, const gva::AttnBwdIn &X, const gva::AttnBwdOut &O,
+                         float *part, size_t part_floats_avail, hipStream_t st, gva::PtvDrop drop) {
     using namespace gva;
-    if (!g_A && !(Wp2 && bp2 && gva_bwd_point_local(k, c, g))) return PTV2_ERR_ARG;
-#define ARGS n, k, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, g_A, g_sw, gW1, gsc, gsh, gWw2, gbw2, ga, gb, part, part_floats_avail, st, Wp2, bp2, drop
-    if (g == 6 && c == 48) return launch_bwd_point<6, 48, 1>(ARGS);
-    if (g == 12 && c == 96) return launch_bwd_point<12, 96, 1>(ARGS);
-    if (g == 24 && c == 192) return launch_bwd_point<24, 192, 2>(ARGS);
-    if (g == 48 && c == 384) return launch_bwd_point<48, 384, 4>(ARGS);
-    if (g == 64 && c == 512) return launch_bwd_point<64, 512, 4>(ARGS);
-#undef ARGS
+    if (!X.g_A && !(I.Wp2 && I.bp2 && gva_bwd_point_local(k, c, g))) return PTV2_ERR_ARG;
+    if (g == 6 && c == 48) return launch_bwd_point<6, 48, 1>(n, k, I, X, O, part, part_floats_avail, st, drop);
+    if (g == 12 && c == 96) return launch_bwd_point<12, 96, 1>(n, k, I, X, O, part, part_floats_avail, st, drop);
+    if (g == 24 && c == 192) return launch_bwd_point<24, 192, 2>(n, k, I, X, O, part, part_floats_avail, st, drop);
+    if (g == 48 && c == 384) return launch_bwd_point<48, 384, 4>(n, k, I, X, O, part, part_floats_avail, st, drop);
+    if (g == 64 && c == 512) return launch_bwd_point<64, 512, 4>(n, k, I, X, O, part, part_floats_avail, st, drop);
     return PTV2_ERR_ARG;
 }

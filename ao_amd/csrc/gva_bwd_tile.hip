@@ -550,10 +550,8 @@ __global__ __launch_bounds__(256, G <= 24 ? 2 : 1) void attention_bwd_tile_mixed
 }
 
 template <int G, int C>
-static int launch_bwd_tile_mixed(int n, int nfull, const float *W1, const float *sc, const float *sh, const float *Ww2, const float *bw2,
-                                 const float *v, const float *a, const float *b, const float *coord, const int *idx, const float *g_out,
-                                 const float *Wp2, const float *bp2, float *gW1, float *gsc, float *gsh, float *gWw2, float *gbw2, float *ga,
-                                 float *gb, float *part, size_t part_floats_avail, PtvDrop drop, hipStream_t st) {
+static int launch_bwd_tile_mixed(int n, int nfull, const AttnIn &I, const AttnBwdIn &X, const AttnBwdOut &O, float *part,
+                                 size_t part_floats_avail, PtvDrop drop, hipStream_t st) {
     using K8 = BwdTileCfg<G, C, 8>;
     using K4 = BwdTileCfg<G, C, 4>;
     static_assert(K8::PF == K4::PF, "one record format");
@@ -568,8 +566,9 @@ static int launch_bwd_tile_mixed(int n, int nfull, const float *W1, const float 
     const int ntail = (int)((n - (long long)nfull * 8 + 3) / 4);
     const int nblk = nfull + ntail;
     if ((size_t)nblk * K8::PF > part_floats_avail) return PTV2_ERR_WORKSPACE;
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, nfull, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, Wp2, bp2, gW1, part, drop);
-    launch_finalize(st, (const float *)part, nblk, K8::PF, MapBwdPoint{ga, gb, gsc, gsh, gWw2, gbw2, C, G});
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, nfull, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.v, I.a, I.b, I.coord, I.idx,
+                       X.g_out, I.Wp2, I.bp2, O.gW1, part, drop);
+    launch_finalize(st, (const float *)part, nblk, K8::PF, MapBwdPoint{O.ga, O.gb, O.gsc, O.gsh, O.gWw2, O.gbw2, C, G});
     return PTV2_OK;
 }
 // whole rounds of resident workgroups the 8-point tiles fill, when what is left is at most half a round (else 0: plain launch)
@@ -592,10 +591,8 @@ static int bwd_tile_full_rounds(int n) {
 }
 
 template <int G, int C, int TP>
-static int launch_bwd_tile(int n, const float *W1, const float *sc, const float *sh, const float *Ww2, const float *bw2, const float *v,
-                           const float *a, const float *b, const float *coord, const int *idx, const float *g_out, const float *Wp2,
-                           const float *bp2, float *gW1, float *gsc, float *gsh, float *gWw2, float *gbw2, float *ga, float *gb,
-                           float *part, size_t part_floats_avail, PtvDrop drop, hipStream_t st) {
+static int launch_bwd_tile(int n, const AttnIn &I, const AttnBwdIn &X, const AttnBwdOut &O, float *part, size_t part_floats_avail,
+                           PtvDrop drop, hipStream_t st) {
     using K = BwdTileCfg<G, C, TP>;
     const size_t lds = sizeof(float) * K::lds_floats;
     const bool dropping = drop.thresh != 0;
@@ -607,8 +604,9 @@ static int launch_bwd_tile(int n, const float *W1, const float *sc, const float 
     }
     const int nblk = (n + TP - 1) / TP;
     if ((size_t)nblk * K::PF > part_floats_avail) return PTV2_ERR_WORKSPACE;
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, Wp2, bp2, gW1, part, drop);
-    launch_finalize(st, (const float *)part, nblk, K::PF, MapBwdPoint{ga, gb, gsc, gsh, gWw2, gbw2, C, G});
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.v, I.a, I.b, I.coord, I.idx, X.g_out,
+                       I.Wp2, I.bp2, O.gW1, part, drop);
+    launch_finalize(st, (const float *)part, nblk, K::PF, MapBwdPoint{O.ga, O.gb, O.gsc, O.gsh, O.gWw2, O.gbw2, C, G});
     return PTV2_OK;
 }
 
@@ -628,24 +626,19 @@ size_t gva_bwd_tile_part_floats(int n, int c, int g) {
 
 // the softmax / aggregation backward with the grouped projection's backward folded in: reads g_out (never g_A / g_sw);
 // writes gW1 (n,16,g) and, through the finalize, gsc, gsh (g), gWw2 (g,g), gbw2 (g), ga (c,3), gb (c)
-int gva_bwd_tile_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                        const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
-                        const float *g_out, const float *Wp2, const float *bp2, float *gW1, float *gsc, float *gsh, float *gWw2,
-                        float *gbw2, float *ga, float *gb, float *part, size_t part_floats_avail, gva::PtvDrop drop, hipStream_t st) {
+int gva_bwd_tile_launch(int n, int k, int c, int g, const gva::AttnIn &I, const gva::AttnBwdIn &X, const gva::AttnBwdOut &O,
+                        float *part, size_t part_floats_avail, gva::PtvDrop drop, hipStream_t st) {
     using namespace gva;
     if (!gva_bwd_tile_supported(k, c, g) || n < 1) return PTV2_ERR_ARG;
-#define ARGS n, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, Wp2, bp2, gW1, gsc, gsh, gWw2, gbw2, ga, gb, part, part_floats_avail, drop, st
     if (g == 12 || g == 24) {
         const int nfull = g == 12 ? bwd_tile_full_rounds<12, 96>(n) : bwd_tile_full_rounds<24, 192>(n);
-#define MARGS n, nfull, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, g_out, Wp2, bp2, gW1, gsc, gsh, gWw2, gbw2, ga, gb, part, part_floats_avail, drop, st
-        if (nfull) return g == 12 ? launch_bwd_tile_mixed<12, 96>(MARGS) : launch_bwd_tile_mixed<24, 192>(MARGS);
-#undef MARGS
+        if (nfull && g == 12) return launch_bwd_tile_mixed<12, 96>(n, nfull, I, X, O, part, part_floats_avail, drop, st);
+        if (nfull) return launch_bwd_tile_mixed<24, 192>(n, nfull, I, X, O, part, part_floats_avail, drop, st);
     }
-    if (g == 12) return launch_bwd_tile<12, 96, 8>(ARGS);
-    if (g == 24) return launch_bwd_tile<24, 192, 8>(ARGS);
+    if (g == 12) return launch_bwd_tile<12, 96, 8>(n, I, X, O, part, part_floats_avail, drop, st);
+    if (g == 24) return launch_bwd_tile<24, 192, 8>(n, I, X, O, part, part_floats_avail, drop, st);
     // one workgroup per CU at this width: tiles of 4 points while they all fit in ONE round of the 256 CUs (n = 240: 61 us against
     // 80), tiles of 8 beyond (n = 1074: 135 workgroups, 86 us; 269 tiles of 4 would be two rounds, 120 us)
-    if ((n + 3) / 4 <= 256) return launch_bwd_tile<48, 384, 4>(ARGS);
-    return launch_bwd_tile<48, 384, 8>(ARGS);
-#undef ARGS
+    if ((n + 3) / 4 <= 256) return launch_bwd_tile<48, 384, 4>(n, I, X, O, part, part_floats_avail, drop, st);
+    return launch_bwd_tile<48, 384, 8>(n, I, X, O, part, part_floats_avail, drop, st);
 }

@@ -554,6 +554,32 @@ __device__ __forceinline__ void fold_w_bwd_channel(const FoldWBwdArgs &A, int j,
     }
 }
 
+// ---- operand bundles of the internal attention interfaces (internal.h) ----------------------------------------------------
+// Host side only: a bundle names the operands that travel together through the host functions and is unpacked into a
+// kernel's positional arguments where the kernel is launched; it is never a kernel argument itself.  The fields carry the
+// names of ptv2_gva_block / ptv2_gva_block_grads.  A field a form does not use is NULL.
+struct AttnIn {  // what every softmax / aggregation form reads; Wp2 / bp2: the forms that fold the grouped projection in
+    const float *W1, *sc, *sh, *Ww2, *bw2, *v, *a, *b, *coord, *Wp2, *bp2;
+    const int *idx;
+};
+struct AttnFwdOut { float *w, *sw, *A, *out_v, *out, *stats; };  // out_v: the staged form only; A, stats may be NULL
+struct AttnBwdIn {  // w, sw: saved by the forward; g_A / g_sw: both, or neither where the form works from Wp2 / bp2
+    const float *w, *sw, *g_out, *g_A, *g_sw;
+    const int *inv_ptr, *inv_rows;
+};
+struct AttnBwdOut { float *gW1, *gsc, *gsh, *gWw2, *gbw2, *gv, *ga, *gb; };
+struct LogitsIn {  // (the backward reads a, b, M, coord, idx)
+    const float *kW, *qW, *a, *b, *M, *cW, *coord;
+    const int *idx;
+};
+struct LogitsOut { float *W1; double *T1, *T2; };
+struct LogitsBwdIn {  // gT1 / gT2: NULL where FoldWBwdArgs derives them
+    const float *W1, *gW1;
+    const double *gT1, *gT2;
+    const int *inv_ptr, *inv_rows;
+};
+struct LogitsBwdOut { float *gkW, *gqW, *ga, *gb, *gM, *gcW; };
+
 // "last block" tail of the logits kernels: column sums -> T1, T2 (-> folded affine)
 __device__ __forceinline__ void finalize_logit_sums(const float *part, int nblk, int g, double *T1, double *T2,
                                                     const FoldWFwdArgs &F) {

@@ -277,10 +277,8 @@ extern "C" int gva_pos_moments_hip_launcher(int n, int k, const float *coord, co
 }
 
 // F.sc != NULL: the final reduction also folds BN_w (block runtime); the C entry point below passes none
-int gva_logits_forward_fold(const GvaPlan &P, int n, int k, int c, int g, const float *kW, const float *qW, const float *a,
-                            const float *b,
-                            const float *M, const float *cW, const float *coord, const int *idx, float *W1, double *T1, double *T2,
-                            const gva::FoldWFwdArgs &F, void *workspace, size_t workspace_bytes, void *stream) {
+int gva_logits_forward_fold(const GvaPlan &P, int n, int k, int c, int g, const LogitsIn &I, const LogitsOut &O,
+                            const FoldWFwdArgs &F, void *workspace, size_t workspace_bytes, void *stream) {
     if (n < 0 || k < 1 || c < 1 || g < 1) return PTV2_ERR_ARG;
     if (!workspace || workspace_bytes < gva_workspace_bytes(n, k, c, g)) return PTV2_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -289,8 +287,8 @@ int gva_logits_forward_fold(const GvaPlan &P, int n, int k, int c, int g, const 
     if (P.logits_fwd != GvaPlan::LF_ROWS) {
         PtvScopedTimer t(KID_LOGITS_FWD, st, 4.0 * ((double)n * k * (g + 1) + (double)n * (3 + 2 * g)));
         const int rc = P.logits_fwd == GvaPlan::LF_MFMA
-                           ? gva_logits_fwd_mfma_launch(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st)
-                           : gva_logits_point_launch(n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, part, T1, T2, F, st);
+                           ? gva_logits_fwd_mfma_launch(n, k, c, g, I, O, part, F, st)
+                           : gva_logits_point_launch(n, k, c, g, I, O, part, F, st);
         if (rc != PTV2_OK) return rc;
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
@@ -311,14 +309,14 @@ int gva_logits_forward_fold(const GvaPlan &P, int n, int k, int c, int g, const 
         if (lds > 32 * 1024)                                                                                       \
             (void)hipFuncSetAttribute((const void *)logits_fwd_kernel<GG, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                       (int)lds);                                                                   \
-        hipLaunchKernelGGL((logits_fwd_kernel<GG, 4>), dim3(nblk), dim3(TPB), lds, st, n, k, c, kW, qW, a, b, M, cW, coord, \
-                           idx, W1, part, cnt ? cnt + CNT_LOGITS_FWD : nullptr, T1, T2, F);                                                                         \
+        hipLaunchKernelGGL((logits_fwd_kernel<GG, 4>), dim3(nblk), dim3(TPB), lds, st, n, k, c, I.kW, I.qW, I.a, I.b, I.M, I.cW, \
+                           I.coord, I.idx, O.W1, part, cnt ? cnt + CNT_LOGITS_FWD : nullptr, O.T1, O.T2, F);                       \
     } else {                                                                                                       \
         if (lds > 32 * 1024)                                                                                       \
             (void)hipFuncSetAttribute((const void *)logits_fwd_kernel<GG, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                       (int)lds);                                                                   \
-        hipLaunchKernelGGL((logits_fwd_kernel<GG, 1>), dim3(nblk), dim3(TPB), lds, st, n, k, c, kW, qW, a, b, M, cW, coord, \
-                           idx, W1, part, cnt ? cnt + CNT_LOGITS_FWD : nullptr, T1, T2, F);                                                                         \
+        hipLaunchKernelGGL((logits_fwd_kernel<GG, 1>), dim3(nblk), dim3(TPB), lds, st, n, k, c, I.kW, I.qW, I.a, I.b, I.M, I.cW, \
+                           I.coord, I.idx, O.W1, part, cnt ? cnt + CNT_LOGITS_FWD : nullptr, O.T1, O.T2, F);                       \
     }
     {
         // idx, coord, kW (unique rows once), qW in; W1 out
@@ -326,7 +324,7 @@ int gva_logits_forward_fold(const GvaPlan &P, int n, int k, int c, int g, const 
         GVA_DISPATCH_G(g, CALL)
     }
 #undef CALL
-    if (!own_final) hipLaunchKernelGGL(finalize_logit_sums_kernel, dim3((g + FLS_GROUPS - 1) / FLS_GROUPS), dim3(1024), 0, st, (const float *)part, nblk, g, T1, T2, F);
+    if (!own_final) hipLaunchKernelGGL(finalize_logit_sums_kernel, dim3((g + FLS_GROUPS - 1) / FLS_GROUPS), dim3(1024), 0, st, (const float *)part, nblk, g, O.T1, O.T2, F);
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
 }
@@ -335,7 +333,9 @@ extern "C" int gva_logits_forward_hip_launcher(int n, int k, int c, int g, const
                                                const float *a, const float *b, const float *M, const float *cW,
                                                const float *coord, const int *idx, float *W1, double *T1, double *T2,
                                                void *workspace, size_t workspace_bytes, void *stream) {
-    return gva_logits_forward_fold(gva_plan(n, k, c, g, false, true), n, k, c, g, kW, qW, a, b, M, cW, coord, idx, W1, T1, T2,
-                                   gva::FoldWFwdArgs{}, workspace,
-                                   workspace_bytes, stream);
+    LogitsIn I{};
+    I.kW = kW; I.qW = qW; I.a = a; I.b = b; I.M = M; I.cW = cW; I.coord = coord; I.idx = idx;
+    LogitsOut O{};
+    O.W1 = W1; O.T1 = T1; O.T2 = T2;
+    return gva_logits_forward_fold(gva_plan(n, k, c, g, false, true), n, k, c, g, I, O, FoldWFwdArgs{}, workspace, workspace_bytes, stream);
 }

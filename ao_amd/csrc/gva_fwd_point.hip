@@ -331,12 +331,9 @@ int gva_fwd_point_supported(int k, int c, int g) { return k == 16 && c == 48 && 
 // the kernel addresses with 32-bit byte offsets (A is the largest tensor: 6 x 48 floats per point) and rounds n up to 64
 int gva_fwd_point_max_n() { return (int)((0x7fffffffu / (4u * 6 * 48)) & ~63u) - 64; }
 
-// softmax + aggregation + grouped projection of one attention forward; stats (may be NULL): per-64-row-block column statistics
-// of `out` ([ceil(n / 64)][2 c] floats, the record form of gva_peb_forward_stats)
-int gva_fwd_point_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                         const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
-                         const float *Wp2, const float *bp2, float *w, float *sw, float *A, float *out, float *stats,
-                         void *stream) {
+// softmax + aggregation + grouped projection of one attention forward; O.stats (may be NULL): per-64-row-block column statistics
+// of O.out ([ceil(n / 64)][2 c] floats, the record form of gva_peb_forward_stats)
+int gva_fwd_point_launch(int n, int k, int c, int g, const gva::AttnIn &I, const gva::AttnFwdOut &O, void *stream) {
     using namespace gva;
     if (!gva_fwd_point_supported(k, c, g) || n < 1 || n > gva_fwd_point_max_n()) return PTV2_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -353,12 +350,9 @@ int gva_fwd_point_launch(int n, int k, int c, int g, const float *W1, const floa
     const int grid = (nblk + rounds - 1) / rounds;
     // W1 + idx + coord + v rows (each unique row once) in; w, sw, A, out out
     PtvScopedTimer t(KID_FWD_POINT, st, 4.0 * ((double)n * k * (2 * g + 1) + (double)n * (3 + 2 * c + g) + (double)n * g * c));
-    if (stats)
-        hipLaunchKernelGGL(attention_fwd_point6_kernel<true>, dim3(grid), dim3(256), 0, st, n, nblk, W1, sc, sh, Ww2, bw2, v, a, b, coord,
-                           idx, Wp2, bp2, w, sw, A, out, stats);
-    else
-        hipLaunchKernelGGL(attention_fwd_point6_kernel<false>, dim3(grid), dim3(256), 0, st, n, nblk, W1, sc, sh, Ww2, bw2, v, a, b, coord,
-                           idx, Wp2, bp2, w, sw, A, out, stats);
+    auto kern = O.stats ? attention_fwd_point6_kernel<true> : attention_fwd_point6_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, n, nblk, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.v, I.a, I.b, I.coord, I.idx, I.Wp2,
+                       I.bp2, O.w, O.sw, O.A, O.out, O.stats);
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
 }

@@ -335,21 +335,19 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_tile_kernel(
 }
 
 template <int G, int C, int GB>
-static int launch_fwd_tile(int n, const float *W1, const float *sc, const float *sh, const float *Ww2, const float *bw2, const float *v,
-                           const float *a, const float *b, const float *coord, const int *idx, const float *Wp2, const float *bp2,
-                           float *w, float *sw, float *out, float *stats, float *a_out, PtvDrop drop, hipStream_t st) {
+static int launch_fwd_tile(int n, const AttnIn &I, const AttnFwdOut &O, PtvDrop drop, hipStream_t st) {
     using K = FwdTileCfg<G, C, GB>;
     const size_t lds = sizeof(float) * K::lds_floats;
     const bool dropping = drop.thresh != 0;
-    auto kern = a_out ? (dropping ? attention_fwd_tile_kernel<G, C, GB, true, true> : attention_fwd_tile_kernel<G, C, GB, true, false>)
+    auto kern = O.A ? (dropping ? attention_fwd_tile_kernel<G, C, GB, true, true> : attention_fwd_tile_kernel<G, C, GB, true, false>)
                       : (dropping ? attention_fwd_tile_kernel<G, C, GB, false, true> : attention_fwd_tile_kernel<G, C, GB, false, false>);
     static bool configured[2][2] = {{false, false}, {false, false}};
-    if (!configured[a_out != nullptr][dropping]) {
+    if (!configured[O.A != nullptr][dropping]) {
         if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PTV2_ERR_LAUNCH;
-        configured[a_out != nullptr][dropping] = true;
+        configured[O.A != nullptr][dropping] = true;
     }
-    hipLaunchKernelGGL(kern, dim3((n + 15) / 16, G / GB), dim3(256), lds, st, n, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, Wp2, bp2, w,
-                       sw, out, stats, a_out, drop);
+    hipLaunchKernelGGL(kern, dim3((n + 15) / 16, G / GB), dim3(256), lds, st, n, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.v, I.a, I.b, I.coord,
+                       I.idx, I.Wp2, I.bp2, O.w, O.sw, O.out, O.stats, O.A, drop);
     return PTV2_OK;
 }
 
@@ -362,11 +360,9 @@ int gva_fwd_tile_supported(int k, int c, int g) {
 // rows per statistics record of gva_fwd_tile_launch
 int gva_fwd_tile_stat_rows() { return 16; }
 
-// softmax + aggregation + grouped projection of one attention forward.  stats (may be NULL): column statistics of `out` per
-// 16-row tile, [ceil(n / 16)][2 c] floats (sum, sum of squares about the tile mean); a_out (may be NULL): A (n, g, c)
-int gva_fwd_tile_launch(int n, int k, int c, int g, const float *W1, const float *sc, const float *sh, const float *Ww2,
-                        const float *bw2, const float *v, const float *a, const float *b, const float *coord, const int *idx,
-                        const float *Wp2, const float *bp2, float *w, float *sw, float *out, float *stats, float *a_out, void *stream) {
+// softmax + aggregation + grouped projection of one attention forward.  O.stats (may be NULL): column statistics of O.out per
+// 16-row tile, [ceil(n / 16)][2 c] floats (sum, sum of squares about the tile mean); O.A (may be NULL): A (n, g, c)
+int gva_fwd_tile_launch(int n, int k, int c, int g, const gva::AttnIn &I, const gva::AttnFwdOut &O, void *stream) {
     using namespace gva;
     if (!gva_fwd_tile_supported(k, c, g) || n < 1) return PTV2_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -375,12 +371,10 @@ int gva_fwd_tile_launch(int n, int k, int c, int g, const float *W1, const float
                      4.0 * ((double)n * k * (2 * g + 1) + (double)n * (3 + 2 * c + g)));
     int rc;
     const PtvDrop drop = ptv2_attn_drop_current();  // (0 outside a gva_block call with attention dropout)
-#define ARGS n, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, Wp2, bp2, w, sw, out, stats, a_out, drop, st
-    if (g == 12) rc = launch_fwd_tile<12, 96, 12>(ARGS);
-    else if (g == 24) rc = launch_fwd_tile<24, 192, 12>(ARGS);
-    else if (g == 48) rc = launch_fwd_tile<48, 384, 12>(ARGS);
-    else rc = launch_fwd_tile<64, 512, 16>(ARGS);
-#undef ARGS
+    if (g == 12) rc = launch_fwd_tile<12, 96, 12>(n, I, O, drop, st);
+    else if (g == 24) rc = launch_fwd_tile<24, 192, 12>(n, I, O, drop, st);
+    else if (g == 48) rc = launch_fwd_tile<48, 384, 12>(n, I, O, drop, st);
+    else rc = launch_fwd_tile<64, 512, 16>(n, I, O, drop, st);
     if (rc != PTV2_OK) return rc;
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
@@ -392,5 +386,10 @@ extern "C" int gva_attention_forward_hip_launcher(int n, int k, int c, int g, co
                                                   const float *bp2, float *w, float *sw, float *out, float *A, void *stream) {
     if (!W1 || !sc || !sh || !Ww2 || !bw2 || !v || !a || !b || !coord || !idx || !Wp2 || !bp2 || !w || !sw || !out) return PTV2_ERR_ARG;
     if (n == 0) return PTV2_OK;
-    return gva_fwd_tile_launch(n, k, c, g, W1, sc, sh, Ww2, bw2, v, a, b, coord, idx, Wp2, bp2, w, sw, out, nullptr, A, stream);
+    gva::AttnIn I{};
+    I.W1 = W1; I.sc = sc; I.sh = sh; I.Ww2 = Ww2; I.bw2 = bw2; I.v = v; I.a = a; I.b = b; I.coord = coord; I.idx = idx;
+    I.Wp2 = Wp2; I.bp2 = bp2;
+    gva::AttnFwdOut O{};
+    O.w = w; O.sw = sw; O.out = out; O.A = A;
+    return gva_fwd_tile_launch(n, k, c, g, I, O, stream);
 }

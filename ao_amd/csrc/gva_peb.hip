@@ -362,29 +362,27 @@ using namespace gva;
         default: return PTV2_ERR_ARG;  \
     }
 
-// internal (gva_block.hip): stats != NULL asks for the per-64-row-block column statistics of `out` (bn_tiles_floats(n, c)
-// floats; see peb_fwd_mfma_kernel); *stats_done tells whether this call produced them (the matrix-core form only)
-int gva_peb_forward_stats(int n, int c, int g, const float *A, const float *Wp2, const float *bp2, const float *sw,
-                          const float *out_v, float *out, float *stats, int *stats_done, void *stream);
-
 extern "C" int gva_peb_forward_hip_launcher(int n, int c, int g, const float *A, const float *Wp2, const float *bp2,
                                             const float *sw, const float *out_v, float *out, void *stream) {
-    return gva_peb_forward_stats(n, c, g, A, Wp2, bp2, sw, out_v, out, nullptr, nullptr, stream);
+    AttnIn I{};
+    I.Wp2 = Wp2; I.bp2 = bp2;
+    AttnFwdOut O{};  // (A, sw, out_v are read only)
+    O.A = const_cast<float *>(A); O.sw = const_cast<float *>(sw); O.out_v = const_cast<float *>(out_v); O.out = out;
+    return gva_peb_forward_stats(n, c, g, I, O, nullptr, stream);
 }
 
 template <int C, int GPW>
-static void launch_peb_mfma_g(int n, int g, const float *A, const float *Wp2, const float *bp2, const float *sw, const float *out_v,
-                              float *out, float *stats, hipStream_t st) {
+static void launch_peb_mfma_g(int n, int g, const AttnIn &I, const AttnFwdOut &O, hipStream_t st) {
     const int nrb = (n + 63) / 64;
     const size_t lds = sizeof(float) * ((size_t)GPW * 8 * (C + 8) + 4 * GPW * 8);
     auto kern = peb_fwd_mfma_kernel<C, GPW>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(nrb, (g + GPW - 1) / GPW), dim3(TPB), lds, st, n, g, A, Wp2, bp2, sw, out_v, out, stats);
+    hipLaunchKernelGGL(kern, dim3(nrb, (g + GPW - 1) / GPW), dim3(TPB), lds, st, n, g, (const float *)O.A, I.Wp2, I.bp2,
+                       (const float *)O.sw, (const float *)O.out_v, O.out, O.stats);
 }
 
 template <int C>
-static void launch_peb_mfma(int n, int g, const float *A, const float *Wp2, const float *bp2, const float *sw, const float *out_v,
-                            float *out, float *stats, hipStream_t st) {
+static void launch_peb_mfma(int n, int g, const AttnIn &I, const AttnFwdOut &O, hipStream_t st) {
     const int nrb = (n + 63) / 64;
     // groups per workgroup: as many (of 6, 3, 2, 1) as keep >= ~512 workgroups in the launch (each stages its Wp2 rows once)
     const int opts[4] = {6, 3, 2, 1};
@@ -392,15 +390,16 @@ static void launch_peb_mfma(int n, int g, const float *A, const float *Wp2, cons
     for (int i = 0; i < 4; ++i)
         if ((long long)nrb * ((g + opts[i] - 1) / opts[i]) >= 512 || opts[i] == 1) { gpw = opts[i]; break; }
     switch (gpw) {
-        case 6: launch_peb_mfma_g<C, 6>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
-        case 3: launch_peb_mfma_g<C, 3>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
-        case 2: launch_peb_mfma_g<C, 2>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
-        default: launch_peb_mfma_g<C, 1>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
+        case 6: launch_peb_mfma_g<C, 6>(n, g, I, O, st); break;
+        case 3: launch_peb_mfma_g<C, 3>(n, g, I, O, st); break;
+        case 2: launch_peb_mfma_g<C, 2>(n, g, I, O, st); break;
+        default: launch_peb_mfma_g<C, 1>(n, g, I, O, st); break;
     }
 }
 
-int gva_peb_forward_stats(int n, int c, int g, const float *A, const float *Wp2, const float *bp2, const float *sw,
-                          const float *out_v, float *out, float *stats, int *stats_done, void *stream) {
+// internal (gva_block.hip): O.stats != NULL asks for the per-64-row-block column statistics of O.out (bn_tiles_floats(n, c)
+// floats; see peb_fwd_mfma_kernel); *stats_done tells whether this call produced them (the matrix-core form only)
+int gva_peb_forward_stats(int n, int c, int g, const AttnIn &I, const AttnFwdOut &O, int *stats_done, void *stream) {
     if (n < 0 || c < 4 || g < 1 || c % g != 0 || c % 4 != 0) return PTV2_ERR_ARG;
     if (stats_done) *stats_done = 0;
     if (n == 0) return PTV2_OK;
@@ -408,13 +407,13 @@ int gva_peb_forward_stats(int n, int c, int g, const float *A, const float *Wp2,
         hipStream_t st = (hipStream_t)stream;
         PtvScopedTimer t(KID_PEB_FWD, st, 4.0 * ((double)n * g * c + 2.0 * n * c + (double)n * g + (double)c * c));
         switch (c) {
-            case 48: launch_peb_mfma<48>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
-            case 96: launch_peb_mfma<96>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
-            case 192: launch_peb_mfma<192>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
-            case 384: launch_peb_mfma<384>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
-            default: launch_peb_mfma<512>(n, g, A, Wp2, bp2, sw, out_v, out, stats, st); break;
+            case 48: launch_peb_mfma<48>(n, g, I, O, st); break;
+            case 96: launch_peb_mfma<96>(n, g, I, O, st); break;
+            case 192: launch_peb_mfma<192>(n, g, I, O, st); break;
+            case 384: launch_peb_mfma<384>(n, g, I, O, st); break;
+            default: launch_peb_mfma<512>(n, g, I, O, st); break;
         }
-        if (stats && stats_done) *stats_done = 64;
+        if (O.stats && stats_done) *stats_done = 64;
         PTV2_CHECK_LAUNCH();
         return PTV2_OK;
     }
@@ -437,8 +436,8 @@ int gva_peb_forward_stats(int n, int c, int g, const float *A, const float *Wp2,
         (void)hipFuncSetAttribute((const void *)peb_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     {
         PtvScopedTimer t(KID_PEB_FWD, (hipStream_t)stream, 4.0 * ((double)n * g * c + 2.0 * n * c + (double)n * g + (double)c * c));
-        hipLaunchKernelGGL(peb_fwd_kernel, dim3(gx, ny), dim3(TPB), lds, (hipStream_t)stream, n, c, g, ct, A, Wp2,
-                           bp2, sw, out_v, out);
+        hipLaunchKernelGGL(peb_fwd_kernel, dim3(gx, ny), dim3(TPB), lds, (hipStream_t)stream, n, c, g, ct, (const float *)O.A, I.Wp2,
+                           I.bp2, (const float *)O.sw, (const float *)O.out_v, O.out);
     }
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;

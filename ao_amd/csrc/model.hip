@@ -22,7 +22,7 @@
 #include <mutex>
 #include <vector>
 
-#include "common.h"
+#include "dense_common.h"
 
 namespace {
 
@@ -365,6 +365,17 @@ bool wgrad_defer_enabled() {
 
 bool use_batch(const ptv2_model *M, const ptv2_linbn &L) { return M->training || !L.run_mean || !L.run_var; }
 
+// the BatchNorm of a Linear + BatchNorm layer as the record-fed launchers take it (64-row records in `part`, no folded affine);
+// the only place that decides whether the running buffers are tracked
+dense::BnTileSet linbn_set(const ptv2_model *M, const ptv2_linbn &L, const LinBnSaved &S, float *part) {
+    const bool track = M->training && L.run_mean && L.run_var;
+    dense::BnTileSet T{};
+    T.part = part; T.rb = 64;
+    T.mean = S.mean; T.rstd = S.rstd; T.gamma = L.gamma; T.beta = L.beta;
+    if (track) { T.run_mean = L.run_mean; T.run_var = L.run_var; T.batches = L.batches; }
+    return T;
+}
+
 // h = x W^T + b (row GEMM, or the narrow kernel when cin is not a multiple of 4); y = ReLU(BN(h)).  `y` may differ from
 // the arena slot (the skip branch of the unpool writes the unpool's output buffer).
 int linbn_forward(const ptv2_model *M, const ptv2_linbn &L, const LinBnSaved &S, int n, const float *x, float *y, const Work &W,
@@ -374,16 +385,12 @@ int linbn_forward(const ptv2_model *M, const ptv2_linbn &L, const LinBnSaved &S,
     // applies BatchNorm + ReLU (three launches otherwise: statistics, finalize, apply)
     if (use_batch(M, L) && L.cin % 4 == 0 && L.cout % 4 == 0 && (n + 63) / 64 <= 512 &&
         sizeof(float) * bn_tiles_floats(n, L.cout) <= W.dense_bytes) {
-        const bool track = M->training && L.run_mean && L.run_var;
+        const dense::BnTileSet T = linbn_set(M, L, S, (float *)W.dense);
         const float *xs[1] = {x}, *ws[1] = {L.w}, *bs[1] = {L.b};
         float *ys[1] = {S.h}, *sts[1] = {(float *)W.dense};
         RUN(rows_gemm_fused_hip_launcher(n, L.cout, L.cin, 1, 0, xs, ws, 0, L.b ? bs : nullptr, ys, 0, nullptr, nullptr, sts, stream));
-        if (bn_tiles_apply_relu(n, L.cout, (float *)W.dense, L.gamma, L.beta, S.mean, S.rstd, track ? L.run_mean : nullptr,
-                                track ? L.run_var : nullptr, track ? L.batches : nullptr, M->eps, M->momentum, S.h, y, stream))
-            return PTV2_OK;
-        RUN(bn_tiles_finalize_hip_launcher(n, L.cout, (float *)W.dense, L.gamma, L.beta, S.mean, S.rstd, nullptr, nullptr,
-                                           track ? L.run_mean : nullptr, track ? L.run_var : nullptr, track ? L.batches : nullptr,
-                                           M->eps, M->momentum, stream));
+        if (bn_tiles_apply_relu(n, L.cout, T, M->eps, M->momentum, S.h, y, stream)) return PTV2_OK;
+        RUN(bn_tiles_finalize_rb(n, L.cout, T, M->eps, M->momentum, stream));
         RUN(bn_apply_hip_launcher(n, L.cout, S.h, S.mean, S.rstd, L.gamma, L.beta, 1, y, stream));
         return PTV2_OK;
     }
@@ -395,10 +402,9 @@ int linbn_forward(const ptv2_model *M, const ptv2_linbn &L, const LinBnSaved &S,
                            L.cout, x, L.w, L.b, S.h);
     }
     if (use_batch(M, L)) {
-        const bool track = M->training && L.run_mean && L.run_var;
-        RUN(bn_forward_hip_launcher(n, L.cout, S.h, L.gamma, L.beta, 1, S.mean, S.rstd, track ? L.run_mean : nullptr,
-                                    track ? L.run_var : nullptr, track ? L.batches : nullptr, M->eps, M->momentum, nullptr, nullptr,
-                                    y, W.dense, W.dense_bytes, stream));
+        const dense::BnTileSet T = linbn_set(M, L, S, nullptr);
+        RUN(bn_forward_hip_launcher(n, L.cout, S.h, T.gamma, T.beta, 1, T.mean, T.rstd, T.run_mean, T.run_var, T.batches, M->eps,
+                                    M->momentum, nullptr, nullptr, y, W.dense, W.dense_bytes, stream));
     } else {
         hipLaunchKernelGGL(bn_eval_moments_kernel, dim3(divup(L.cout, 256)), dim3(256), 0, st, L.cout, (const float *)L.run_mean,
                            (const float *)L.run_var, M->eps, S.mean, S.rstd);

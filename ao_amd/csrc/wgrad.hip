@@ -709,14 +709,14 @@ int ptv2_wgrad_defer_flush(void *stream) {
 // internal (gva_block.hip): the grouped projection's weight gradient with A recomputed from the saved softmax weights
 // (gva_wgrad_tile.hip): dW (g, 8, c) and db (g, 8) = sum_n g_out sw.  Filed when the caller's backward defers (the operands
 // outlive the Block), else launched here with its finalize; PTV2_ERR_ARG for shapes without an instance
-int gva_wp2_wgrad_recompute(int n, int k, int c, int g, const float *g_out, const float *w, const float *sw, const float *a,
-                            const float *b, const float *coord, const int *idx, float *dW, float *db, void *workspace,
-                            size_t workspace_bytes, void *stream) {
-    if (!gva_wgrad_tile_supported(k, c, g) || n < 1 || !g_out || !w || !sw || !a || !b || !coord || !idx || !dW || !db) return PTV2_ERR_ARG;
+int gva_wp2_wgrad_recompute(int n, int k, int c, int g, const gva::AttnIn &I, const gva::AttnBwdIn &X, float *dW, float *db,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+    if (!gva_wgrad_tile_supported(k, c, g) || n < 1 || !X.g_out || !X.w || !X.sw || !I.a || !I.b || !I.coord || !I.idx || !dW || !db)
+        return PTV2_ERR_ARG;
     WgradJob J{};
     J.n = n; J.cin = c; J.batch = g;
-    J.gY = g_out; J.X = w; J.rowscale = sw; J.dW = dW; J.db = db;
-    J.aux[0] = coord; J.aux[1] = idx; J.aux[2] = a; J.aux[3] = b;
+    J.gY = X.g_out; J.X = X.w; J.rowscale = X.sw; J.dW = dW; J.db = db;
+    J.aux[0] = I.coord; J.aux[1] = I.idx; J.aux[2] = I.a; J.aux[3] = I.b;
     const double algo = 4.0 * ((double)n * (c + 16.0 * g + g + 16 + 3) + (double)c * c + c);  // g_out, w, sw, idx, coord in; dW, db out
     if (g_wdefer.active && g_wdefer.armed_rs && (int)g_wdefer.jobs[5].size() < WGRAD_MAX_JOBS) {
         const size_t floats = gva_wgrad_tile_plan(&J, n / 128 + 1);
@@ -752,7 +752,11 @@ extern "C" int gva_attention_wgrad_hip_launcher(int n, int k, int c, int g, cons
                                                 float *dbp2, void *workspace, size_t workspace_bytes, void *stream) {
     if (!gva_wgrad_tile_supported(k, c, g) || n < 0) return PTV2_ERR_ARG;
     if (n == 0) return PTV2_OK;
-    return gva_wp2_wgrad_recompute(n, k, c, g, g_out, w, sw, a, b, coord, idx, dWp2, dbp2, workspace, workspace_bytes, stream);
+    gva::AttnIn I{};
+    I.a = a; I.b = b; I.coord = coord; I.idx = idx;
+    gva::AttnBwdIn X{};
+    X.g_out = g_out; X.w = w; X.sw = sw;
+    return gva_wp2_wgrad_recompute(n, k, c, g, I, X, dWp2, dbp2, workspace, workspace_bytes, stream);
 }
 
 extern "C" int linear_wgrad_strided_hip_launcher(int n, int cout, int cin, int batch, const float *gY, long long ldy,

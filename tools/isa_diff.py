@@ -7,7 +7,8 @@ kernel metadata read (llvm-readelf --notes).  Compared over the whole library, w
   * per symbol the instruction text (addresses and encodings stripped; branch targets are relative to their symbol;
     pc-relative references to device data and the fill between functions normalised, see functions()),
   * per kernel vgpr / sgpr count, LDS, scratch and kernarg sizes.
-A symbol that several objects emit (a static kernel defined in a header) must be identical in all of them.
+A symbol that several objects emit (a static kernel defined in a header) is compared as the set of its distinct copies:
+one copy where every unit is built alike, two where a unit has flags of its own (augment.o: contraction off).
 Prints the differing symbols and exits 1 if there are any.  Reads nothing outside the two directories (the unbundled
 code objects go to a scratch subdirectory of each, removed again)."""
 import glob, os, re, shutil, subprocess, sys
@@ -32,10 +33,12 @@ def data_symbols(code_object):
 
 def functions(code_object):
     """symbol -> instruction text, with what depends on where the linker put things taken out:
-    a 32-bit literal that, added to the address of its own instruction, lands inside a data object of the code object is a
-    pc-relative reference to it (every unit has its own copy of the header's static device data, at its own distance from
-    the code) and is written as <object+offset>; the fill behind the end of a function (the run of one repeated line that
-    closes it, longest behind the last function of an object) is dropped."""
+    a 32-bit literal of a scalar add (the s_add_u32 behind s_getpc_b64: the only way an address is formed) that, added to the
+    address of its own instruction, lands inside a data object of the code object is a pc-relative reference to it (every
+    unit has its own copy of the header's static device data, at its own distance from the code) and is written as
+    <object+offset>; any other literal is compared as it stands (a vector instruction's constant such as 0xfffffe00 lands in
+    some kernel descriptor as soon as the unit is large enough).  The fill behind the end of a function (the run of one
+    repeated line that closes it, longest behind the last function of an object) is dropped."""
     data = data_symbols(code_object)
     out, name = {}, None
     for line in run("llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", code_object).splitlines():
@@ -46,7 +49,7 @@ def functions(code_object):
         elif name and line.strip() not in ("", "...") and not line.startswith("Disassembly"):  # ("...": zero fill)
             text, _, comment = line.partition("//")
             lit, at = re.search(r"\b0x([0-9a-f]{8})\b", text), re.match(r"\s*([0-9A-Fa-f]+):", comment)
-            if lit and at:
+            if lit and at and text.split()[0] in ("s_add_u32", "s_addc_u32"):
                 v = int(lit.group(1), 16)
                 target = int(at.group(1), 16) + (v - (1 << 32) if v >> 31 else v)
                 for addr, size, sym in data:
@@ -104,9 +107,10 @@ def main():
     for sym in sorted(set(a) | set(b)):
         if sym not in a or sym not in b:
             bad.append((sym, "only in " + (sys.argv[1] if sym in a else sys.argv[2])))
-        elif len(a[sym]) != 1 or len(b[sym]) != 1:
-            bad.append((sym, "copies differ within one build"))
         elif a[sym] != b[sym]:
+            if len(a[sym]) != 1 or len(b[sym]) != 1:
+                bad.append((sym, "%d distinct copies -> %d, not the same ones" % (len(a[sym]), len(b[sym]))))
+                continue
             (ta, ma), (tb, mb) = next(iter(a[sym])), next(iter(b[sym]))
             bad.append((sym, "instructions differ" if ta != tb else "metadata %s -> %s" % (ma, mb)))
     kernels = sum(1 for s in a if next(iter(a[s]))[1] is not None)
