@@ -121,3 +121,10 @@ if not os.path.exists(REFINE_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % REFINE_HEADER)
 with open(REFINE_HEADER) as _f:
     refine_consts, refine_structs, refine_signatures = parse(_f.read())
+
+# the fourth public header (the PP2S label pipeline: bridges, weak labels, mask votes), likewise
+PP2S_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_pp2s_hip.h")
+if not os.path.exists(PP2S_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % PP2S_HEADER)
+with open(PP2S_HEADER) as _f:
+    pp2s_consts, pp2s_structs, pp2s_signatures = parse(_f.read())

@@ -30,6 +30,8 @@ EXPECTED_ABI = 11
 EXPECTED_DATA_ABI = 1
 # the same for include/ptv2_refine_hip.h and ptv2_refine_abi_version() (ao_amd/csrc/refine.hip)
 EXPECTED_REFINE_ABI = 1
+# the same for include/ptv2_pp2s_hip.h and ptv2_pp2s_abi_version() (ao_amd/csrc/pp2s.hip)
+EXPECTED_PP2S_ABI = 1
 
 
 def build(verbose=False):
@@ -47,7 +49,7 @@ def lib():
                 "ao_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C ao_amd/csrc` (needs hipcc). There is no CPU fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures):
+        for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures, _abi.pp2s_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -68,6 +70,10 @@ def lib():
         if have != EXPECTED_REFINE_ABI:
             raise RuntimeError("ao_amd: %s has refine ABI version %d, the python side expects %d -- stale build; rebuild with "
                                "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_REFINE_ABI))
+        have = handle.ptv2_pp2s_abi_version()
+        if have != EXPECTED_PP2S_ABI:
+            raise RuntimeError("ao_amd: %s has pp2s ABI version %d, the python side expects %d -- stale build; rebuild with "
+                               "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_PP2S_ABI))
         for which, name in enumerate(("ptv2_aug_step", "ptv2_aug_program")):
             if handle.ptv2_data_struct_bytes(which) != ctypes.sizeof(_abi.data_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

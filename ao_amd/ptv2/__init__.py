@@ -18,3 +18,5 @@ from .losses import LovaszLoss, lovasz_softmax  # noqa: F401
 from .cac import CACSegmentor  # noqa: F401
 from .tester import SemSegTester, VoteTable, test_scene  # noqa: F401
 from .refine import LabelRefiner, grid_cells, grid_prompts, refine_scene, scene_confidence  # noqa: F401
+from .pp2s import (LabelPropagator, align_room, bridge_to_numpy, choose_weak_labels, pp2s_scene,  # noqa: F401
+                   project_view)
