@@ -343,16 +343,16 @@ extern "C" int ptv2_block_backward_hip_launcher(const ptv2_block *B, const ptv2_
     if (!G->inv_ptr) (void)ptv2_zero_async(gv, sizeof(float) * (size_t)n * c, (hipStream_t)stream);
     // the attention backward's last launch (the skinny input gradients gk, gq) also leaves the reduce records of the two
     // BatchNorm backwards that consume them (skinny.hip skinny_bn_bwd_reduce_kernel): one launch fewer per Block
-    if (batch[1] == batch[2]) {
-        const float *xs[2] = {S.hk, S.hq}, *gys[2] = {gk, gq}, *ms[2] = {S.mean[2], S.mean[1]}, *rs[2] = {S.rstd[2], S.rstd[1]};
-        const float *gs[2] = {P[PTV2_BLK_KN_G], P[PTV2_BLK_QN_G]}, *bs[2] = {P[PTV2_BLK_KN_B], P[PTV2_BLK_QN_B]};
-        ptv2_skinny_bn_arm(n, c, xs, gys, ms, rs, gs, bs, 1, W.dense, W.dense_bytes);
+    {
+        const PtvSkinnyBnScope skinny;
+        if (batch[1] == batch[2]) {
+            const float *xs[2] = {S.hk, S.hq}, *gys[2] = {gk, gq}, *ms[2] = {S.mean[2], S.mean[1]}, *rs[2] = {S.rstd[2], S.rstd[1]};
+            const float *gs[2] = {P[PTV2_BLK_KN_G], P[PTV2_BLK_QN_G]}, *bs[2] = {P[PTV2_BLK_KN_B], P[PTV2_BLK_QN_B]};
+            ptv2_skinny_bn_arm(n, c, xs, gys, ms, rs, gs, bs, 1, W.dense, W.dense_bytes);
+        }
+        const PtvWgradArmRs arm(kept != nullptr);
+        RUN(gva_block_backward_hip_launcher(&V, &VG, W.gva, W.gva_bytes, stream));
     }
-    ptv2_wgrad_defer_arm_rs(kept != nullptr);
-    const int grc = gva_block_backward_hip_launcher(&V, &VG, W.gva, W.gva_bytes, stream);
-    ptv2_wgrad_defer_arm_rs(false);
-    ptv2_skinny_bn_disarm();
-    RUN(grc);
     // linear_k / linear_q BatchNorm + ReLU
     if (batch[1] == batch[2]) {  // one reduce / finalize / apply for both
         const float *xs[2] = {S.hk, S.hq}, *gys[2] = {gk, gq}, *ms[2] = {S.mean[2], S.mean[1]}, *rs[2] = {S.rstd[2], S.rstd[1]};
@@ -389,10 +389,8 @@ extern "C" int ptv2_block_backward_hip_launcher(const ptv2_block *B, const ptv2_
         const float *xsh[5] = {S.bsh[5], S.bsh[0], S.bsh[0], S.bsh[0], nullptr};
         float *dws[5] = {GP(PTV2_BLK_FC3_W), GP(PTV2_BLK_Q_W), GP(PTV2_BLK_K_W), GP(PTV2_BLK_V_W), GP(PTV2_BLK_FC1_W)};
         float *dbs[5] = {nullptr, GPB(PTV2_BLK_Q_B), GPB(PTV2_BLK_K_B), GPB(PTV2_BLK_V_B), nullptr};
-        ptv2_wgrad_defer_arm(kept != nullptr);
-        const int wrc = linear_wgrad_multi_hip_launcher(n, c, c, 5, gys, xs, dws, dbs, xsc, xsh, W.dense, W.dense_bytes, stream);
-        ptv2_wgrad_defer_arm(false);
-        RUN(wrc);
+        const PtvWgradArm arm(kept != nullptr);
+        RUN(linear_wgrad_multi_hip_launcher(n, c, c, 5, gys, xs, dws, dbs, xsc, xsh, W.dense, W.dense_bytes, stream));
     }
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;

@@ -108,9 +108,22 @@ int ptv2_zero_async(void *p, size_t bytes, hipStream_t st);
 void ptv2_wgrad_defer_begin(void *arena, size_t bytes);   // arena: job table + operands that must outlive their Block + records
 bool ptv2_wgrad_defer_active();
 float *ptv2_wgrad_defer_alloc(size_t floats);             // NULL: not deferring, or no room (the caller launches at once)
-void ptv2_wgrad_defer_arm(bool on);                       // the next weight-gradient call may be filed (its operands are kept)
+void ptv2_wgrad_defer_arm(bool on);                       // the weight-gradient calls that follow may be filed (their operands are kept)
 void ptv2_wgrad_defer_arm_rs(bool on);                    // ... the row-scaled strided form inside the attention backward
 bool ptv2_wgrad_defer_armed_rs();
+// armed for the callee(s) of a scope, whatever way it is left
+struct PtvWgradArm {
+    explicit PtvWgradArm(bool on) { ptv2_wgrad_defer_arm(on); }
+    ~PtvWgradArm() { ptv2_wgrad_defer_arm(false); }
+    PtvWgradArm(const PtvWgradArm &) = delete;
+    PtvWgradArm &operator=(const PtvWgradArm &) = delete;
+};
+struct PtvWgradArmRs {
+    explicit PtvWgradArmRs(bool on) { ptv2_wgrad_defer_arm_rs(on); }
+    ~PtvWgradArmRs() { ptv2_wgrad_defer_arm_rs(false); }
+    PtvWgradArmRs(const PtvWgradArmRs &) = delete;
+    PtvWgradArmRs &operator=(const PtvWgradArmRs &) = delete;
+};
 int ptv2_wgrad_defer_flush(void *stream);                 // run what has been filed
 void ptv2_wgrad_defer_end();
 size_t ptv2_wgrad_defer_table_bytes();

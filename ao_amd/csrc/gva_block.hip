@@ -534,10 +534,8 @@ extern "C" int gva_block_backward_hip_launcher(const ptv2_gva_block *B, const pt
         const float *gys[2] = {W.gkW, W.gqW}, *xs[2] = {B->key, B->q};
         float *dws[2] = {W.gWw1_k, W.gWw1_q};
         const float *xsc[2] = {B->k_sc, B->q_sc}, *xsh[2] = {B->k_sh, B->q_sh};
-        ptv2_wgrad_defer_arm(kq_kept);
-        const int krc = linear_wgrad_multi_hip_launcher(n, g, c, 2, gys, xs, dws, nullptr, xsc, xsh, W.kq_part, W.kq_bytes, stream);
-        ptv2_wgrad_defer_arm(false);
-        RUN(krc);
+        const PtvWgradArm arm(kq_kept);
+        RUN(linear_wgrad_multi_hip_launcher(n, g, c, 2, gys, xs, dws, nullptr, xsc, xsh, W.kq_part, W.kq_bytes, stream));
     }
     }
     {

@@ -38,6 +38,12 @@ void ptv2_skinny_bn_arm(int n, int c, const float *const *x, const float *const 
                         const float *const *rstd, const float *const *gamma, const float *const *beta, int relu, void *workspace,
                         size_t workspace_bytes);
 void ptv2_skinny_bn_disarm(void);
+struct PtvSkinnyBnScope {  // disarmed when the scope that may have armed it is left
+    PtvSkinnyBnScope() = default;
+    ~PtvSkinnyBnScope() { ptv2_skinny_bn_disarm(); }
+    PtvSkinnyBnScope(const PtvSkinnyBnScope &) = delete;
+    PtvSkinnyBnScope &operator=(const PtvSkinnyBnScope &) = delete;
+};
 int skinny_backward_pair_bn_reduce(int n, int cin, int cout, const float *const *gy, const float *W, float *const *gx,
                                    void *stream);
 int ptv2_skinny_bn_take_records(int n, int c, const float *part, const float *const *gy);

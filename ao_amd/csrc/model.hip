@@ -426,10 +426,8 @@ int linbn_backward(const ptv2_model *M, const ptv2_linbn &L, const LinBnSaved &S
         if (L.cin % 4 != 0 || L.cout % 4 != 0) return PTV2_ERR_ARG;
         RUN(rows_gemm_hip_launcher(n, L.cin, L.cout, gh, L.w, 1, nullptr, gx, accumulate, stream));
     }
-    ptv2_wgrad_defer_arm(kept != nullptr);
-    const int rc = linear_wgrad_hip_launcher(n, L.cout, L.cin, gh, x, L.gw, L.b ? L.gb : nullptr, W.dense, W.dense_bytes, stream);
-    ptv2_wgrad_defer_arm(false);
-    return rc;
+    const PtvWgradArm arm(kept != nullptr);
+    return linear_wgrad_hip_launcher(n, L.cout, L.cin, gh, x, L.gw, L.b ? L.gb : nullptr, W.dense, W.dense_bytes, stream);
 }
 
 void fill_block(const ptv2_model *M, int q, int j, const Arena &A, const float *x, ptv2_block *B) {

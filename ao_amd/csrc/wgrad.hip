@@ -1,8 +1,10 @@
 // ao_amd/csrc/wgrad.hip -- the weight gradient of nn.Linear, dW = dY^T X (the bias gradient falls out of the same pass), as a
 // split-K reduction over row chunks on gfx950: the direct and the LDS-staged MFMA forms (one product, a strided batch, up to six
-// products of one shape, row-scaled bias sums), the grouped projection's form on the vector ALUs, and the deferred file
-// (WgradDefer, ptv2_wgrad_defer_*): inside a model backward the launches are filed where they are called and run by one launch
-// per kernel form at its end through a job table (wgrad_job.h); the recompute form of gva_wgrad_tile.hip is filed here too.
+// products of one shape, row-scaled bias sums) and the grouped projection's form on the vector ALUs.  Every entry point
+// describes its call ONCE, as a WgradJob (wgrad_job.h) inside a WgradCall (plan_*), and hands it to wgrad_submit, which either
+// launches it at once with its finalize -- the kernel takes the job by value -- or, inside a model backward, files it (WgradDefer,
+// ptv2_wgrad_defer_*): the filed jobs of a backward are run at its end by one launch per kernel form through a job table.  The
+// recompute form of gva_wgrad_tile.hip is planned there and submitted here too.
 //
 // Why these exist.  The weight gradients have a 48x48 .. 384x384 output with K = N up to 1.2e5, for which the BLAS picks a
 // 9-workgroup kernel (353 us per call); this is a pure HBM streaming problem: each workgroup owns a 48x48 output tile for a
@@ -22,14 +24,6 @@ namespace dense {
 // output tile for one chunk of rows; the waves interleave k-steps and are summed through LDS.
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int WG_MT = 3, WG_TILE = 16 * WG_MT, WG_CHUNK = 256, WG_CHUNK_MIN = 128;
-
-// several independent products of one shape in one launch (blockIdx.z selects the operand pair)
-struct WgradMulti {
-    const float *gY[6], *X[6];
-    float *dW[6], *db[6];
-    int count;  // 0: the strided form (gY + z * sy, X + z * sx)
-    const float *xsc[6], *xsh[6];  // != NULL: the X operand of pair z is ReLU(x * xsc + xsh) (fused BatchNorm + ReLU)
-};
 
 // BF16: the U = 8 k-steps of a trip (8 rows per lane and fragment) are exactly the 8-per-lane operand of
 // V_MFMA_F32_16X16X32_BF16: 8 fp32 MFMAs per tile pair become one instruction on bf16-rounded operands.
@@ -153,17 +147,19 @@ __device__ __forceinline__ void wgrad_direct_tile(const int n, const int cout, c
     }
 }
 
+// job + workgroup coordinates (bx: row chunk, by: output tile, bz: product) -> the tile; count > 0: the multi form, an operand
+// pair per product (several independent products of one shape in one launch), else the strided form (gY + bz * sy, X + bz * sx)
 template <bool BF16>
-__global__ __launch_bounds__(TPB) void linear_wgrad_kernel(int n, int cout, int cin, int tiles_i,
-                                                           const float *__restrict__ gY, long long ldy, long long sy,
-                                                           const float *__restrict__ X, long long ldx, long long sx,
-                                                           float *__restrict__ part, float *__restrict__ part_b,
-                                                           int batch, WgradMulti multi, int chunk) {
-    const int bz = blockIdx.z;
-    wgrad_direct_tile<BF16>(n, cout, cin, tiles_i, multi.count ? multi.gY[bz] : gY + (long long)bz * sy, ldy,
-                            multi.count ? multi.X[bz] : X + (long long)bz * sx, ldx, part, part_b != nullptr, batch,
-                            multi.count ? multi.xsc[bz] : nullptr, multi.count ? multi.xsh[bz] : nullptr, chunk,
-                            (int)blockIdx.x, (int)blockIdx.y, bz);
+__device__ __forceinline__ void wgrad_direct_job(const WgradJob &J, const int bx, const int by, const int bz) {
+    const bool multi = J.count > 0;
+    wgrad_direct_tile<BF16>(J.n, J.cout, J.cin, J.tiles_i, multi ? J.mgY[bz] : J.gY + (long long)bz * J.sy, J.ldy,
+                            multi ? J.mX[bz] : J.X + (long long)bz * J.sx, J.ldx, J.part, J.has_pb != 0, J.batch,
+                            multi ? J.mxsc[bz] : nullptr, multi ? J.mxsh[bz] : nullptr, J.chunk, bx, by, bz);
+}
+// one call: the job by value, grid (chunks, tiles, products)
+template <bool BF16>
+__global__ __launch_bounds__(TPB) void linear_wgrad_kernel(WgradJob J) {
+    wgrad_direct_job<BF16>(J, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
 }
 
 // ---- the same reduction with the operands staged through LDS (fp32 matrix cores) ---------------------------------------
@@ -320,17 +316,15 @@ __device__ __forceinline__ void wgrad_lds_tile(const int n, const int cout, cons
 }
 
 template <int RS>
-__global__ __launch_bounds__(TPB) void linear_wgrad_lds_kernel(int n, int cout, int cin, int tiles_i,
-                                                               const float *__restrict__ gY, long long ldy, long long sy,
-                                                               const float *__restrict__ X, long long ldx, long long sx,
-                                                               float *__restrict__ part, float *__restrict__ part_b,
-                                                               int batch, WgradMulti multi, int chunk,
-                                                               const float *__restrict__ rowscale, long long lds_s) {
-    const int bz = blockIdx.z;
-    wgrad_lds_tile<RS>(n, cout, cin, tiles_i, multi.count ? multi.gY[bz] : gY + (long long)bz * sy, ldy,
-                       multi.count ? multi.X[bz] : X + (long long)bz * sx, ldx, part, part_b != nullptr, batch,
-                       multi.count ? multi.xsc[bz] : nullptr, multi.count ? multi.xsh[bz] : nullptr, chunk, rowscale, lds_s,
-                       (int)blockIdx.x, (int)blockIdx.y, bz);
+__device__ __forceinline__ void wgrad_lds_job(const WgradJob &J, const int bx, const int by, const int bz) {
+    const bool multi = J.count > 0;
+    wgrad_lds_tile<RS>(J.n, J.cout, J.cin, J.tiles_i, multi ? J.mgY[bz] : J.gY + (long long)bz * J.sy, J.ldy,
+                       multi ? J.mX[bz] : J.X + (long long)bz * J.sx, J.ldx, J.part, J.has_pb != 0, J.batch,
+                       multi ? J.mxsc[bz] : nullptr, multi ? J.mxsh[bz] : nullptr, J.chunk, J.rowscale, J.lds_s, bx, by, bz);
+}
+template <int RS>
+__global__ __launch_bounds__(TPB) void linear_wgrad_lds_kernel(WgradJob J) {
+    wgrad_lds_job<RS>(J, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
 }
 
 // ---- the deferred launches of a whole backward in one launch ------------------------------------------------------------
@@ -354,11 +348,8 @@ __global__ __launch_bounds__(TPB) void linear_wgrad_lds_kernel_jobs(const WgradJ
     while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].wg0) ++j;  // (uniform: scalar loads)
     const WgradJob &J = jobs[j];
     const int local = (int)blockIdx.x - J.wg0;
-    const int bx = local % J.chunks, rest = local / J.chunks, by = rest % J.tiles, bz = rest / J.tiles;
-    const bool multi = J.count > 0;
-    wgrad_lds_tile<RS>(J.n, J.cout, J.cin, J.tiles_i, multi ? J.mgY[bz] : J.gY + (long long)bz * J.sy, J.ldy,
-                       multi ? J.mX[bz] : J.X + (long long)bz * J.sx, J.ldx, J.part, J.has_pb != 0, J.batch,
-                       multi ? J.mxsc[bz] : nullptr, multi ? J.mxsh[bz] : nullptr, J.chunk, J.rowscale, J.lds_s, bx, by, bz);
+    const int rest = local / J.chunks;
+    wgrad_lds_job<RS>(J, local % J.chunks, rest % J.tiles, rest / J.tiles);
 }
 
 // ---- the grouped projection's weight gradient on the vector ALUs ---------------------------------------------------------------
@@ -479,11 +470,8 @@ __global__ __launch_bounds__(TPB) void linear_wgrad_kernel_jobs(const WgradJob *
     while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].wg0) ++j;
     const WgradJob &J = jobs[j];
     const int local = (int)blockIdx.x - J.wg0;
-    const int bx = local % J.chunks, rest = local / J.chunks, by = rest % J.tiles, bz = rest / J.tiles;
-    const bool multi = J.count > 0;
-    wgrad_direct_tile<BF16>(J.n, J.cout, J.cin, J.tiles_i, multi ? J.mgY[bz] : J.gY + (long long)bz * J.sy, J.ldy,
-                            multi ? J.mX[bz] : J.X + (long long)bz * J.sx, J.ldx, J.part, J.has_pb != 0, J.batch,
-                            multi ? J.mxsc[bz] : nullptr, multi ? J.mxsh[bz] : nullptr, J.chunk, bx, by, bz);
+    const int rest = local / J.chunks;
+    wgrad_direct_job<BF16>(J, local % J.chunks, rest % J.tiles, rest / J.tiles);
 }
 
 // the records of all jobs -> their outputs.  A job's slots are whole workgroups.  With up to 32 chunk records a thread sums one
@@ -586,22 +574,50 @@ static int wg_chunk(int n, int tiles, bool filed = false) {
     return (int)std::min<long long>(chunk, 1 << 20);
 }
 
-// ---- deferred weight-gradient launches (see WgradJob) ----------------------------------------------------------------------
+// ---- one description per call, one place that files or launches it ---------------------------------------------------------
 namespace {
-constexpr int WGRAD_FORMS = 6;
+// the kernel forms: a table of filed jobs, a batched launch and a kernel-timer id each
+enum WgradForm { WF_LDS = 0, WF_LDS_RS, WF_DIRECT, WF_DIRECT_BF16, WF_GROUPED, WF_RECOMPUTE, WGRAD_FORMS };
+constexpr int wgrad_kid(WgradForm f) {
+    return f == WF_RECOMPUTE ? KID_WGRAD_TILE : f == WF_GROUPED ? KID_WGRAD_GROUPED : (f == WF_LDS || f == WF_LDS_RS) ? KID_WGRAD_LDS : KID_WGRAD;
+}
+// a planned call: the job as the kernels and the finalize read it (part is set by wgrad_submit) and what only the host needs
+struct WgradCall {
+    WgradJob J;
+    WgradForm form;
+    double bytes;   // algorithmic bytes, strict: every operand read once, every result written once (the split-K partial
+                    // records of this implementation are its own overhead, not the op's)
+    size_t posrel;  // (recompute form, filed) floats of the relative-position buffer behind the records, written at the flush
+};
+
 struct WgradDefer {
     bool active = false;
     bool armed = false;          // the call in progress may be filed (set by the call sites whose operands outlive their Block)
     bool armed_rs = false;       // ... the row-scaled strided form (the grouped projection's weight gradient inside the attention)
-    char *arena = nullptr;       // [job table RS = 0 | job table RS = 1 | kept operands and chunk records]
+    char *arena = nullptr;       // [a job table per form | kept operands and chunk records]
     size_t cap = 0, used = 0;
-    // filed since the last flush, per kernel form: LDS-staged (RS = 0 / 1), direct fp32, direct bf16, grouped, grouped with A recomputed
-    std::vector<WgradJob> jobs[WGRAD_FORMS];
-    double bytes[WGRAD_FORMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // their algorithmic bytes (kernel timer)
+    std::vector<WgradJob> jobs[WGRAD_FORMS];  // filed since the last flush
+    double bytes[WGRAD_FORMS] = {};           // their algorithmic bytes (kernel timer)
 };
 thread_local WgradDefer g_wdefer;
 constexpr int WGRAD_MAX_JOBS = 64;
 constexpr size_t WGRAD_TABLE_BYTES = ptv2_align256(sizeof(WgradJob) * WGRAD_MAX_JOBS);
+
+// the caller armed the file for this call (rs: the row-scaled strided form and the recompute form)
+bool may_file(bool rs) { return g_wdefer.active && (rs ? g_wdefer.armed_rs : g_wdefer.armed); }
+
+// the LDS-staged kernels ask for more dynamic LDS than the default limit
+bool wgrad_configure() {
+    static const bool ok = [] {
+        const void *kernels[4] = {(const void *)linear_wgrad_lds_kernel<0>, (const void *)linear_wgrad_lds_kernel<1>,
+                                  (const void *)linear_wgrad_lds_kernel_jobs<0>, (const void *)linear_wgrad_lds_kernel_jobs<1>};
+        bool all = true;
+        for (const void *k : kernels)
+            all = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WL_LDS_BYTES) == hipSuccess && all;
+        return all;
+    }();
+    return ok;
+}
 }  // namespace
 
 void ptv2_wgrad_defer_begin(void *arena, size_t bytes) {
@@ -620,7 +636,7 @@ void ptv2_wgrad_defer_end() {
 }
 void ptv2_wgrad_defer_arm(bool on) { g_wdefer.armed = on && g_wdefer.active; }
 void ptv2_wgrad_defer_arm_rs(bool on) { g_wdefer.armed_rs = on && g_wdefer.active; }
-bool ptv2_wgrad_defer_armed_rs() { return g_wdefer.active && g_wdefer.armed_rs; }
+bool ptv2_wgrad_defer_armed_rs() { return may_file(true); }
 size_t ptv2_wgrad_defer_table_bytes() { return WGRAD_FORMS * WGRAD_TABLE_BYTES; }
 // a slice of the arena that lives until the backward ends (operands a deferred job reads, its records); NULL: no room
 float *ptv2_wgrad_defer_alloc(size_t floats) {
@@ -636,14 +652,9 @@ int ptv2_wgrad_defer_flush(void *stream) {
     WgradDefer &D = g_wdefer;
     if (!D.active) return PTV2_OK;
     hipStream_t st = (hipStream_t)stream;
-    static const bool once = [] {
-        return hipFuncSetAttribute((const void *)linear_wgrad_lds_kernel_jobs<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)WL_LDS_BYTES) == hipSuccess &&
-               hipFuncSetAttribute((const void *)linear_wgrad_lds_kernel_jobs<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)WL_LDS_BYTES) == hipSuccess;
-    }();
-    if (!once) return PTV2_ERR_LAUNCH;
-    for (int form = 0; form < WGRAD_FORMS; ++form) {
+    if (!wgrad_configure()) return PTV2_ERR_LAUNCH;
+    for (int f = 0; f < WGRAD_FORMS; ++f) {
+        const WgradForm form = (WgradForm)f;
         std::vector<WgradJob> &jobs = D.jobs[form];
         if (jobs.empty()) continue;
         WgradJob *table = (WgradJob *)(D.arena + (size_t)form * WGRAD_TABLE_BYTES);
@@ -651,15 +662,16 @@ int ptv2_wgrad_defer_flush(void *stream) {
         // the jobs whose workgroups run longest first (rows per workgroup x the row piece it reads): the backward files the
         // full-resolution patch-embedding Block LAST, and its 150 us workgroups starting at the end of the launch were its tail
         // (bench step 10.53 -> 10.49 ms)
-        std::stable_sort(jobs.begin(), jobs.end(), [form](const WgradJob &a, const WgradJob &b) {
-            const long long wa = (long long)a.chunk * (form >= 4 ? a.gw * a.cin : 1), wb = (long long)b.chunk * (form >= 4 ? b.gw * b.cin : 1);
+        const bool row_pieces = form == WF_GROUPED || form == WF_RECOMPUTE;
+        std::stable_sort(jobs.begin(), jobs.end(), [row_pieces](const WgradJob &a, const WgradJob &b) {
+            const long long wa = (long long)a.chunk * (row_pieces ? a.gw * a.cin : 1), wb = (long long)b.chunk * (row_pieces ? b.gw * b.cin : 1);
             return wa > wb;
         });
         int wgs = 0, fin = 0;
         long long pos_wgs = 0;  // (recompute form: workgroups of the relative-position launch in front of the jobs)
-        bool pos_all = form == 5;
+        bool pos_all = form == WF_RECOMPUTE;
         for (WgradJob &J : jobs) {
-            if (form == 5) {
+            if (form == WF_RECOMPUTE) {
                 J.ldy = pos_wgs;
                 pos_wgs += ((long long)J.n * 16 + 255) / 256;
                 pos_all = pos_all && J.mX[0] != nullptr;
@@ -676,25 +688,22 @@ int ptv2_wgrad_defer_flush(void *stream) {
             hipLaunchKernelGGL(wgrad_jobs_write_kernel, dim3(1), dim3(64), 0, st, pack, cnt, table + at);
         }
         {
-            PtvScopedTimer t(form == 5 ? KID_WGRAD_TILE : form == 4 ? KID_WGRAD_GROUPED : (form < 2 ? KID_WGRAD_LDS : KID_WGRAD), st, D.bytes[form]);
-            if (form == 0)
-                hipLaunchKernelGGL(linear_wgrad_lds_kernel_jobs<0>, dim3((unsigned)wgs), dim3(TPB), WL_LDS_BYTES, st,
-                                   (const WgradJob *)table, njobs);
-            else if (form == 1)
-                hipLaunchKernelGGL(linear_wgrad_lds_kernel_jobs<1>, dim3((unsigned)wgs), dim3(TPB), WL_LDS_BYTES, st,
-                                   (const WgradJob *)table, njobs);
-            else if (form == 2)
-                hipLaunchKernelGGL(linear_wgrad_kernel_jobs<false>, dim3((unsigned)wgs), dim3(TPB), 0, st, (const WgradJob *)table,
-                                   njobs);
-            else if (form == 3)
-                hipLaunchKernelGGL(linear_wgrad_kernel_jobs<true>, dim3((unsigned)wgs), dim3(TPB), 0, st, (const WgradJob *)table,
-                                   njobs);
-            else if (form == 5) {
-                if (gva_wgrad_tile_launch_jobs((const WgradJob *)table, njobs, wgs, pos_all ? (int)pos_wgs : 0, st) != PTV2_OK) return PTV2_ERR_LAUNCH;
-            } else {
-                size_t lds = 0;
-                for (const WgradJob &J : jobs) lds = std::max(lds, grouped_lds_bytes(J.cin, J.gw));
-                hipLaunchKernelGGL(grouped_wgrad_kernel_jobs, dim3((unsigned)wgs), dim3(TPB), lds, st, (const WgradJob *)table, njobs);
+            PtvScopedTimer t(wgrad_kid(form), st, D.bytes[form]);
+            const dim3 grid((unsigned)wgs), block(TPB);
+            const WgradJob *tab = table;
+            switch (form) {
+                case WF_LDS: hipLaunchKernelGGL(linear_wgrad_lds_kernel_jobs<0>, grid, block, WL_LDS_BYTES, st, tab, njobs); break;
+                case WF_LDS_RS: hipLaunchKernelGGL(linear_wgrad_lds_kernel_jobs<1>, grid, block, WL_LDS_BYTES, st, tab, njobs); break;
+                case WF_DIRECT: hipLaunchKernelGGL(linear_wgrad_kernel_jobs<false>, grid, block, 0, st, tab, njobs); break;
+                case WF_DIRECT_BF16: hipLaunchKernelGGL(linear_wgrad_kernel_jobs<true>, grid, block, 0, st, tab, njobs); break;
+                case WF_GROUPED: {
+                    size_t lds = 0;
+                    for (const WgradJob &J : jobs) lds = std::max(lds, grouped_lds_bytes(J.cin, J.gw));
+                    hipLaunchKernelGGL(grouped_wgrad_kernel_jobs, grid, block, lds, st, tab, njobs);
+                    break;
+                }
+                default:
+                    if (gva_wgrad_tile_launch_jobs(tab, njobs, wgs, pos_all ? (int)pos_wgs : 0, st) != PTV2_OK) return PTV2_ERR_LAUNCH;
             }
         }
         hipLaunchKernelGGL(wgrad_jobs_finalize_kernel, dim3((unsigned)((fin + 255) / 256)), dim3(256), 0, st,
@@ -706,43 +715,190 @@ int ptv2_wgrad_defer_flush(void *stream) {
     return PTV2_OK;
 }
 
+// the multi form's finalize: record = [count][cout*cin] weights, then [count][cout] bias sums
+struct MapWgradMulti {
+    float *dW[6], *db[6];
+    int count, wlen, cout;
+    explicit MapWgradMulti(const WgradJob &J) : count(J.count), wlen(J.cout * J.cin), cout(J.cout) {
+        for (int i = 0; i < 6; ++i) { dW[i] = J.mdW[i]; db[i] = J.mdb[i]; }
+    }
+    __device__ void operator()(int e, double v) const {
+        const int wtot = count * wlen;
+        if (e < wtot) {
+            const int b = e / wlen;
+            dW[b][e - b * wlen] = (float)v;
+        } else {
+            const int r = e - wtot, b = r / cout;
+            if (db[b]) db[b][r - b * cout] = (float)v;
+        }
+    }
+};
+
+namespace gva {
+template <> struct RiderOf<MapWgradMulti> {
+    static constexpr bool ok = true;
+    static PtvRider make(const MapWgradMulti &m) {
+        PtvRider r{};
+        r.kind = RIDER_WGRADN;
+        for (int i = 0; i < 6; ++i) { r.p[i] = i < m.count ? m.dW[i] : nullptr; r.p[6 + i] = i < m.count ? m.db[i] : nullptr; }
+        r.i0 = m.wlen; r.i1 = m.cout; r.i2 = m.count;
+        return r;
+    }
+};
+}  // namespace gva
+
+// A planned call is filed -- `file`: the caller armed the file; the form's table and the arena have room: its records go to the
+// arena (the caller's workspace is reused before the flush) -- or launched here with its finalize, records in the caller's
+// workspace.  PTV2_ERR_WORKSPACE: not filed, and the workspace does not hold the call's records (nothing was launched)
+static int wgrad_submit(WgradCall &C, bool file, void *workspace, size_t workspace_bytes, void *stream) {
+    WgradDefer &D = g_wdefer;
+    WgradJob &J = C.J;
+    if (file && (int)D.jobs[C.form].size() < WGRAD_MAX_JOBS) {
+        float *keep = ptv2_wgrad_defer_alloc((size_t)J.chunks * J.rec);
+        float *pos = keep && C.posrel ? ptv2_wgrad_defer_alloc(C.posrel) : nullptr;
+        if (keep && (pos || !C.posrel)) {
+            J.part = keep;
+            if (pos) J.mX[0] = pos;
+            D.jobs[C.form].push_back(J);
+            D.bytes[C.form] += C.bytes;
+            return PTV2_OK;
+        }
+    }
+    const size_t fit = workspace ? workspace_bytes / (sizeof(float) * (size_t)J.rec) : 0;
+    // (the recompute form takes as many point splits as fit, never more than a filed job: the same bits either way)
+    if (C.form == WF_RECOMPUTE && fit >= 1 && fit < (size_t)J.chunks) (void)gva_wgrad_tile_plan(&J, (int)fit);
+    if (fit < (size_t)J.chunks) return PTV2_ERR_WORKSPACE;
+    if (!wgrad_configure()) return PTV2_ERR_LAUNCH;
+    hipStream_t st = (hipStream_t)stream;
+    J.part = (float *)workspace;
+    {
+        PtvScopedTimer t(wgrad_kid(C.form), st, C.bytes);
+        const dim3 grid(J.chunks, J.tiles, J.batch), block(TPB);
+        switch (C.form) {
+            case WF_LDS: hipLaunchKernelGGL(linear_wgrad_lds_kernel<0>, grid, block, WL_LDS_BYTES, st, J); break;
+            case WF_LDS_RS: hipLaunchKernelGGL(linear_wgrad_lds_kernel<1>, grid, block, WL_LDS_BYTES, st, J); break;
+            case WF_DIRECT: hipLaunchKernelGGL(linear_wgrad_kernel<false>, grid, block, 0, st, J); break;
+            case WF_DIRECT_BF16: hipLaunchKernelGGL(linear_wgrad_kernel<true>, grid, block, 0, st, J); break;
+            case WF_GROUPED:
+                hipLaunchKernelGGL(grouped_wgrad_kernel, dim3((unsigned)J.wgs), block, grouped_lds_bytes(J.cin, J.gw), st, J);
+                break;
+            default:
+                if (gva_wgrad_tile_launch_one(J, st) != PTV2_OK) return PTV2_ERR_LAUNCH;
+        }
+    }
+    if (J.count > 0) launch_finalize(st, (const float *)J.part, J.chunks, J.rec, MapWgradMulti(J));
+    else if (J.has_pb) launch_finalize(st, (const float *)J.part, J.chunks, J.rec, gva::MapSplit2<float>{J.dW, J.db, J.batch * J.cout * J.cin});
+    else launch_finalize(st, (const float *)J.part, J.chunks, J.rec, gva::MapVec<float>{J.dW});
+    PTV2_CHECK_LAUNCH();
+    return PTV2_OK;
+}
+
+// geometry of the matrix-core forms: 48 x 48 output tiles x products, row chunks by wg_chunk (`filed`: the armed state, whether
+// or not the file then has room); has_pb and rec by the caller
+static void plan_tiles(WgradJob &J, int n, int cout, int cin, int batch, bool filed) {
+    J.n = n; J.cout = cout; J.cin = cin; J.batch = batch;
+    J.tiles_i = (cin + WG_TILE - 1) / WG_TILE;
+    J.tiles = (cout + WG_TILE - 1) / WG_TILE * J.tiles_i;
+    J.chunk = wg_chunk(n, J.tiles * batch, filed);
+    J.chunks = (n + J.chunk - 1) / J.chunk;
+    J.wgs = J.chunks * J.tiles * batch;
+}
+
+// the strided batch on the matrix cores.  rowscale != NULL asks for weighted bias sums, which only the LDS-staged fp32 kernel
+// forms (WF_LDS_RS); any other kernel leaves db alone (the caller forms the sums itself) and the call is a plain job
+static WgradCall plan_strided(int n, int cout, int cin, int batch, const float *gY, long long ldy, long long sy, const float *X,
+                              long long ldx, long long sx, float *dW, float *db, const float *rowscale, long long lds_s, bool filed) {
+    WgradCall C{};
+    WgradJob &J = C.J;
+    plan_tiles(J, n, cout, cin, batch, filed);
+    const bool use_lds = !ptv2_matmul_bf16() && wgrad_lds_shape_ok(cout, cin) && wgrad_lds_ok(gY, ldy, sy, X, ldx, sx);
+    const bool rs = rowscale && db && use_lds;
+    if (rowscale && !rs) db = nullptr;
+    C.form = ptv2_matmul_bf16() ? WF_DIRECT_BF16 : rs ? WF_LDS_RS : use_lds ? WF_LDS : WF_DIRECT;
+    C.bytes = 4.0 * batch * ((double)n * (cout + cin) + (double)cout * cin + (db ? cout : 0) + (rs ? (double)n : 0.0));
+    J.has_pb = db ? 1 : 0;  // bias partials live behind the weight partials of each chunk record
+    J.rec = batch * (cout * cin + (db ? cout : 0));
+    J.ldy = ldy; J.sy = sy; J.ldx = ldx; J.sx = sx;
+    J.gY = gY; J.X = X; J.dW = dW; J.db = db;
+    if (rs) { J.rowscale = rowscale; J.lds_s = lds_s; }
+    return C;
+}
+
+// the grouped projection's shape (eight output rows per group, operands as the attention backward passes them): the vector-ALU
+// kernel that reads whole row pieces of X (grouped_wgrad_tile); AO_AMD_WP2_GROUPED=0: the strided matrix-core form
+// (also when the matrix products run on bf16 operands: this one is a vector-ALU kernel, exact fp32 either way)
+static bool plan_grouped(WgradCall *C, int n, int cout, int cin, int batch, const float *gY, long long ldy, long long sy,
+                         const float *X, long long ldx, long long sx, float *dW, float *db, const float *rowscale, long long lds_s) {
+    static const bool grouped_on = !ptv2_env_is("AO_AMD_WP2_GROUPED", '0');
+    if (!(grouped_on && rowscale && db && cout == GRP_I && cin % 4 == 0 && cin / 4 <= TPB && ldy == (long long)batch * cout &&
+          sy == cout && ldx == (long long)batch * cin && sx == cin && lds_s == batch && wgrad_lds_ok(gY, ldy, sy, X, ldx, sx)))
+        return false;
+    *C = WgradCall{};
+    WgradJob &J = C->J;
+    const int q = cin / 4;
+    int gw = 1;
+    for (int d = 1; d <= batch; ++d)
+        if (batch % d == 0 && d * q <= TPB) gw = d;
+    const int blocks_g = batch / gw;
+    const int chunks = (int)std::max<long long>(1, std::min<long long>(((long long)n + 127) / 128, std::max(1, 768 / blocks_g)));
+    J.n = n; J.cout = cout; J.cin = cin; J.tiles_i = 1; J.tiles = blocks_g; J.batch = batch; J.gw = gw;
+    J.chunk = (n + chunks - 1) / chunks;
+    J.chunks = (n + J.chunk - 1) / J.chunk;
+    J.wgs = J.chunks * blocks_g;
+    J.has_pb = 1;
+    J.rec = batch * (cout * cin + cout);
+    J.ldy = ldy; J.sy = sy; J.ldx = ldx; J.sx = sx; J.lds_s = lds_s;
+    J.gY = gY; J.X = X; J.rowscale = rowscale; J.dW = dW; J.db = db;
+    C->form = WF_GROUPED;
+    C->bytes = 4.0 * batch * ((double)n * (cout + cin) + (double)cout * cin + cout + (double)n);
+    return true;
+}
+
+// up to six products of one shape, an operand pair each; PTV2_ERR_ARG (geometry filled all the same) for a missing operand
+static int plan_multi(WgradCall *C, int n, int cout, int cin, int count, const float *const *gY, const float *const *X,
+                      float *const *dW, float *const *db, const float *const *xsc, const float *const *xsh, bool filed) {
+    *C = WgradCall{};
+    WgradJob &J = C->J;
+    plan_tiles(J, n, cout, cin, count, filed);
+    J.has_pb = 1;
+    J.count = count;
+    J.rec = count * (cout * cin + cout);
+    J.ldy = cout; J.ldx = cin;
+    bool lds_ok = !ptv2_matmul_bf16() && wgrad_lds_shape_ok(cout, cin);
+    int distinct_x = 0;  // every DISTINCT X is read once (q, k, v share theirs)
+    for (int i = 0; i < count; ++i) {
+        if (!gY[i] || !X[i] || !dW[i]) return PTV2_ERR_ARG;
+        J.mgY[i] = gY[i]; J.mX[i] = X[i]; J.mdW[i] = dW[i]; J.mdb[i] = db ? db[i] : nullptr;
+        J.mxsc[i] = xsc ? xsc[i] : nullptr;
+        J.mxsh[i] = xsh ? xsh[i] : nullptr;
+        if ((J.mxsc[i] == nullptr) != (J.mxsh[i] == nullptr)) return PTV2_ERR_ARG;
+        lds_ok = lds_ok && wgrad_lds_ok(gY[i], cout, 0, X[i], cin, 0);
+        bool seen = false;
+        for (int j = 0; j < i; ++j) seen |= J.mX[j] == J.mX[i] && J.mxsc[j] == J.mxsc[i];
+        distinct_x += !seen;
+    }
+    C->form = ptv2_matmul_bf16() ? WF_DIRECT_BF16 : (lds_ok ? WF_LDS : WF_DIRECT);
+    C->bytes = 4.0 * ((double)count * n * cout + (double)distinct_x * n * cin + (double)count * cout * (cin + 1));
+    return PTV2_OK;
+}
+
 // internal (gva_block.hip): the grouped projection's weight gradient with A recomputed from the saved softmax weights
 // (gva_wgrad_tile.hip): dW (g, 8, c) and db (g, 8) = sum_n g_out sw.  Filed when the caller's backward defers (the operands
-// outlive the Block), else launched here with its finalize; PTV2_ERR_ARG for shapes without an instance
+// outlive the Block), else launched with its finalize; PTV2_ERR_ARG for shapes without an instance
 int gva_wp2_wgrad_recompute(int n, int k, int c, int g, const gva::AttnIn &I, const gva::AttnBwdIn &X, float *dW, float *db,
                             void *workspace, size_t workspace_bytes, void *stream) {
     if (!gva_wgrad_tile_supported(k, c, g) || n < 1 || !X.g_out || !X.w || !X.sw || !I.a || !I.b || !I.coord || !I.idx || !dW || !db)
         return PTV2_ERR_ARG;
-    WgradJob J{};
+    WgradCall C{};
+    WgradJob &J = C.J;
     J.n = n; J.cin = c; J.batch = g;
     J.gY = X.g_out; J.X = X.w; J.rowscale = X.sw; J.dW = dW; J.db = db;
     J.aux[0] = I.coord; J.aux[1] = I.idx; J.aux[2] = I.a; J.aux[3] = I.b;
-    const double algo = 4.0 * ((double)n * (c + 16.0 * g + g + 16 + 3) + (double)c * c + c);  // g_out, w, sw, idx, coord in; dW, db out
-    if (g_wdefer.active && g_wdefer.armed_rs && (int)g_wdefer.jobs[5].size() < WGRAD_MAX_JOBS) {
-        const size_t floats = gva_wgrad_tile_plan(&J, n / 128 + 1);
-        float *keep = ptv2_wgrad_defer_alloc(floats);
-        float *pos = keep ? ptv2_wgrad_defer_alloc((size_t)n * 16 * 4) : nullptr;  // relative positions, written at the flush
-        if (keep && pos) {
-            J.part = keep;
-            J.mX[0] = pos;
-            g_wdefer.jobs[5].push_back(J);
-            g_wdefer.bytes[5] += algo;
-            return PTV2_OK;
-        }
-    }
-    const size_t rec = (size_t)g * (8 * (size_t)c + 8);
-    const int fit = (int)std::min<size_t>(1 << 20, workspace_bytes / (sizeof(float) * rec));
-    if (!workspace || fit < 1) return PTV2_ERR_WORKSPACE;
-    (void)gva_wgrad_tile_plan(&J, std::min(fit, n / 128 + 1));  // (the same split as a filed job: the same bits either way)
-    J.part = (float *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    {
-        PtvScopedTimer t(KID_WGRAD_TILE, st, algo);
-        if (gva_wgrad_tile_launch_one(J, st) != PTV2_OK) return PTV2_ERR_LAUNCH;
-    }
-    launch_finalize(st, (const float *)J.part, J.chunks, (int)rec, gva::MapSplit2<float>{dW, db, g * 8 * c});
-    PTV2_CHECK_LAUNCH();
-    return PTV2_OK;
+    (void)gva_wgrad_tile_plan(&J, n / 128 + 1);
+    C.form = WF_RECOMPUTE;
+    C.bytes = 4.0 * ((double)n * (c + 16.0 * g + g + 16 + 3) + (double)c * c + c);  // g_out, w, sw, idx, coord in; dW, db out
+    C.posrel = (size_t)n * 16 * 4;
+    return wgrad_submit(C, may_file(true), workspace, workspace_bytes, stream);
 }
 
 // the public form of the above (include/ptv2_hip.h): the weight gradient that completes gva_attention_backward_hip_launcher,
@@ -772,164 +928,20 @@ extern "C" int linear_wgrad_strided_rowscale(int n, int cout, int cin, int batch
                                              size_t workspace_bytes, void *stream) {
     if (weighted) *weighted = 0;
     if (n < 1 || cout < 1 || cin < 1 || batch < 1) return PTV2_ERR_ARG;
-    // the grouped projection's shape (eight output rows per group, operands as the attention backward passes them): the
-    // vector-ALU kernel that reads whole row pieces of X (grouped_wgrad_tile); AO_AMD_WP2_GROUPED=0: the strided matrix-core form
-    static const bool grouped_on = !ptv2_env_is("AO_AMD_WP2_GROUPED", '0');
-    // (also when the matrix products run on bf16 operands: this one is a vector-ALU kernel, exact fp32 either way)
-    if (grouped_on && rowscale && db && cout == GRP_I && cin % 4 == 0 && cin / 4 <= TPB &&
-        ldy == (long long)batch * cout && sy == cout && ldx == (long long)batch * cin && sx == cin && lds_s == batch &&
-        wgrad_lds_ok(gY, ldy, sy, X, ldx, sx)) {
-        const int q = cin / 4;
-        int gw = 1;
-        for (int d = 1; d <= batch; ++d)
-            if (batch % d == 0 && d * q <= TPB) gw = d;
-        const int blocks_g = batch / gw;
-        const int chunks = (int)std::max<long long>(1, std::min<long long>(((long long)n + 127) / 128, std::max(1, 768 / blocks_g)));
-        const int chunk = (n + chunks - 1) / chunks;
-        const size_t rec = (size_t)batch * ((size_t)cout * cin + cout);
-        WgradJob J{};
-        J.n = n; J.cout = cout; J.cin = cin; J.tiles_i = 1; J.tiles = blocks_g; J.batch = batch; J.chunk = chunk;
-        J.chunks = (n + chunk - 1) / chunk; J.has_pb = 1; J.count = 0; J.rec = (int)rec; J.gw = gw;
-        J.wgs = J.chunks * blocks_g;
-        J.ldy = ldy; J.sy = sy; J.ldx = ldx; J.sx = sx; J.lds_s = lds_s;
-        J.gY = gY; J.X = X; J.rowscale = rowscale; J.dW = dW; J.db = db;
-        const double algo = 4.0 * batch * ((double)n * (cout + cin) + (double)cout * cin + cout + (double)n);
-        if (g_wdefer.active && g_wdefer.armed_rs && (int)g_wdefer.jobs[4].size() < WGRAD_MAX_JOBS) {
-            float *keep = ptv2_wgrad_defer_alloc((size_t)J.chunks * rec);
-            if (keep) {
-                J.part = keep;
-                g_wdefer.jobs[4].push_back(J);
-                g_wdefer.bytes[4] += algo;
-                if (weighted) *weighted = 1;
-                return PTV2_OK;
-            }
-        }
-        if (workspace && workspace_bytes >= sizeof(float) * (size_t)J.chunks * rec) {
-            hipStream_t st = (hipStream_t)stream;
-            J.part = (float *)workspace;
-            const size_t lds = grouped_lds_bytes(cin, gw);
-            {
-                PtvScopedTimer t(KID_WGRAD_GROUPED, st, algo);
-                hipLaunchKernelGGL(grouped_wgrad_kernel, dim3((unsigned)J.wgs), dim3(TPB), lds, st, J);
-            }
-            launch_finalize(st, (const float *)J.part, J.chunks, (int)rec, gva::MapSplit2<float>{dW, db, batch * cout * cin});
-            if (weighted) *weighted = 1;
-            PTV2_CHECK_LAUNCH();
-            return PTV2_OK;
-        }
+    // (a row-scaled call is armed by the attention's caller, which keeps gY alive until the backward ends; a plain one by
+    // the Linear + BatchNorm layers between the stages)
+    const bool file = may_file(rowscale != nullptr);
+    WgradCall C;
+    if (plan_grouped(&C, n, cout, cin, batch, gY, ldy, sy, X, ldx, sx, dW, db, rowscale, lds_s)) {
+        const int rc = wgrad_submit(C, file, workspace, workspace_bytes, stream);
+        if (rc == PTV2_OK && weighted) *weighted = 1;
+        if (rc != PTV2_ERR_WORKSPACE) return rc;  // (a workspace too small for its records: the matrix-core route)
     }
-    const int tiles_o = (cout + WG_TILE - 1) / WG_TILE, tiles_i = (cin + WG_TILE - 1) / WG_TILE;
-    const int chunk = wg_chunk(n, tiles_o * tiles_i * batch, g_wdefer.active && (rowscale ? g_wdefer.armed_rs : g_wdefer.armed));
-    const int chunks = (n + chunk - 1) / chunk;
-    const size_t need = sizeof(float) * (size_t)chunks * batch * ((size_t)cout * cin + cout);
-    if (!workspace || workspace_bytes < need) return PTV2_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float *part = (float *)workspace;
-    float *part_b = part;  // non-null flag: bias partials live behind the weight partials of each chunk record
-    dim3 grid(chunks, tiles_o * tiles_i, batch);
-    {
-        // algorithmic bytes, strict: every operand read once, every result written once (the split-K partial
-        // records of this implementation are its own overhead, not the op's)
-        const bool use_lds = !ptv2_matmul_bf16() && wgrad_lds_shape_ok(cout, cin) && wgrad_lds_ok(gY, ldy, sy, X, ldx, sx);
-        const bool rs = rowscale && db && use_lds;
-        if (rowscale && !rs) db = nullptr;  // (the caller forms the weighted sums itself)
-        if (rs && weighted) *weighted = 1;
-        const int form = ptv2_matmul_bf16() ? 3 : (use_lds ? 0 : 2);
-        // (also the row-scaled call whose weighted bias sums this path cannot form -- bf16 operands: the caller computes them
-        // itself and has kept gY for the deferral)
-        const bool plain = (!rowscale && g_wdefer.armed) || (rowscale && !rs && g_wdefer.armed_rs);
-        if (plain && g_wdefer.active && (int)g_wdefer.jobs[form].size() < WGRAD_MAX_JOBS) {
-            // (the plain strided form, armed by a caller that keeps gY alive: the Linear + BatchNorm layers between the stages)
-            const size_t rec = (size_t)batch * ((size_t)cout * cin + (db ? cout : 0));
-            float *keep = ptv2_wgrad_defer_alloc((size_t)chunks * rec);
-            if (keep) {
-                WgradJob J{};
-                J.n = n; J.cout = cout; J.cin = cin; J.tiles_i = tiles_i; J.tiles = tiles_o * tiles_i; J.batch = batch;
-                J.chunk = chunk; J.chunks = chunks; J.has_pb = db ? 1 : 0; J.count = 0; J.rec = (int)rec;
-                J.wgs = chunks * J.tiles * J.batch;
-                J.ldy = ldy; J.sy = sy; J.ldx = ldx; J.sx = sx;
-                J.gY = gY; J.X = X; J.part = keep; J.dW = dW; J.db = db;
-                g_wdefer.jobs[form].push_back(J);
-                g_wdefer.bytes[form] += 4.0 * batch * ((double)n * (cout + cin) + (double)cout * cin + (db ? cout : 0));
-                return PTV2_OK;
-            }
-        }
-        if (rs && g_wdefer.active && g_wdefer.armed_rs && (int)g_wdefer.jobs[1].size() < WGRAD_MAX_JOBS) {
-            // inside a model backward (the caller keeps gY alive until its end): filed, run with the other Blocks' (WgradJob)
-            const size_t rec = (size_t)batch * ((size_t)cout * cin + cout);
-            float *keep = ptv2_wgrad_defer_alloc((size_t)chunks * rec);
-            if (keep) {
-                WgradJob J{};
-                J.n = n; J.cout = cout; J.cin = cin; J.tiles_i = tiles_i; J.tiles = tiles_o * tiles_i; J.batch = batch;
-                J.chunk = chunk; J.chunks = chunks; J.has_pb = 1; J.count = 0; J.rec = (int)rec;
-                J.wgs = chunks * J.tiles * J.batch;
-                J.ldy = ldy; J.sy = sy; J.ldx = ldx; J.sx = sx; J.lds_s = lds_s;
-                J.gY = gY; J.X = X; J.rowscale = rowscale; J.part = keep; J.dW = dW; J.db = db;
-                g_wdefer.jobs[1].push_back(J);
-                g_wdefer.bytes[1] += 4.0 * batch * ((double)n * (cout + cin) + (double)cout * cin + cout + (double)n);
-                return PTV2_OK;
-            }
-        }
-        PtvScopedTimer t(use_lds ? KID_WGRAD_LDS : KID_WGRAD, st,
-                         4.0 * batch * ((double)n * (cout + cin) + (double)cout * cin + (db ? cout : 0) + (rs ? (double)n : 0.0)));
-        if (ptv2_matmul_bf16())
-            hipLaunchKernelGGL(linear_wgrad_kernel<true>, grid, dim3(TPB), 0, st, n, cout, cin, tiles_i, gY, ldy, sy, X, ldx, sx, part,
-                               db ? part_b : (float *)nullptr, batch, WgradMulti{}, chunk);
-        else if (use_lds) {
-            static const bool once = [] {
-                return hipFuncSetAttribute((const void *)linear_wgrad_lds_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)WL_LDS_BYTES) == hipSuccess;
-            }();
-            (void)once;
-            if (rs) {
-                static const bool once1 = [] {
-                    return hipFuncSetAttribute((const void *)linear_wgrad_lds_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)WL_LDS_BYTES) == hipSuccess;
-                }();
-                (void)once1;
-                hipLaunchKernelGGL(linear_wgrad_lds_kernel<1>, grid, dim3(TPB), WL_LDS_BYTES, st, n, cout, cin, tiles_i, gY, ldy, sy, X,
-                                   ldx, sx, part, part_b, batch, WgradMulti{}, chunk, rowscale, lds_s);
-            } else
-                hipLaunchKernelGGL(linear_wgrad_lds_kernel<0>, grid, dim3(TPB), WL_LDS_BYTES, st, n, cout, cin, tiles_i, gY, ldy, sy, X,
-                                   ldx, sx, part, db ? part_b : (float *)nullptr, batch, WgradMulti{}, chunk, (const float *)nullptr, 0LL);
-        } else
-            hipLaunchKernelGGL(linear_wgrad_kernel<false>, grid, dim3(TPB), 0, st, n, cout, cin, tiles_i, gY, ldy, sy, X, ldx, sx, part,
-                               db ? part_b : (float *)nullptr, batch, WgradMulti{}, chunk);
-    }
-    if (db) launch_finalize(st, (const float *)part, chunks, batch * cout * cin + batch * cout,
-                            gva::MapSplit2<float>{dW, db, batch * cout * cin});
-    else launch_finalize(st, (const float *)part, chunks, batch * cout * cin, gva::MapVec<float>{dW});
-    PTV2_CHECK_LAUNCH();
-    return PTV2_OK;
+    C = plan_strided(n, cout, cin, batch, gY, ldy, sy, X, ldx, sx, dW, db, rowscale, lds_s, file);
+    if (!workspace || workspace_bytes < sizeof(float) * (size_t)C.J.chunks * batch * ((size_t)cout * cin + cout)) return PTV2_ERR_WORKSPACE;
+    if (C.form == WF_LDS_RS && weighted) *weighted = 1;
+    return wgrad_submit(C, file, workspace, workspace_bytes, stream);
 }
-
-struct MapWgradMulti {  // record = [count][cout*cin] weights, then [count][cout] bias sums
-    WgradMulti m;
-    int wlen, cout;
-    __device__ void operator()(int e, double v) const {
-        const int wtot = m.count * wlen;
-        if (e < wtot) {
-            const int b = e / wlen;
-            m.dW[b][e - b * wlen] = (float)v;
-        } else {
-            const int r = e - wtot, b = r / cout;
-            if (m.db[b]) m.db[b][r - b * cout] = (float)v;
-        }
-    }
-};
-
-namespace gva {
-template <> struct RiderOf<MapWgradMulti> {
-    static constexpr bool ok = true;
-    static PtvRider make(const MapWgradMulti &m) {
-        PtvRider r{};
-        r.kind = RIDER_WGRADN;
-        for (int i = 0; i < 6; ++i) { r.p[i] = i < m.m.count ? m.m.dW[i] : nullptr; r.p[6 + i] = i < m.m.count ? m.m.db[i] : nullptr; }
-        r.i0 = m.wlen; r.i1 = m.cout; r.i2 = m.m.count;
-        return r;
-    }
-};
-}  // namespace gva
 
 // count (<= 6) products dW[i] (cout,cin) = gY[i]^T X[i], db[i] = column sums of gY[i] (db[i] may be NULL), all of one
 // shape and row count, in one launch + one finalize (workspace: dense_workspace_bytes(n, count * cout, cin))
@@ -938,75 +950,12 @@ extern "C" int linear_wgrad_multi_hip_launcher(int n, int cout, int cin, int cou
                                                const float *const *xsc, const float *const *xsh, void *workspace,
                                                size_t workspace_bytes, void *stream) {
     if (n < 1 || cout < 1 || cin < 1 || count < 1 || count > 6 || !gY || !X || !dW) return PTV2_ERR_ARG;
-    const int chunk = wg_chunk(n, ((cout + WG_TILE - 1) / WG_TILE) * ((cin + WG_TILE - 1) / WG_TILE) * count,
-                               g_wdefer.active && g_wdefer.armed);
-    const int chunks = (n + chunk - 1) / chunk;
-    const size_t rec = (size_t)count * ((size_t)cout * cin + cout);
-    if (!workspace || workspace_bytes < sizeof(float) * (size_t)chunks * rec) return PTV2_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    WgradMulti m{};
-    m.count = count;
-    for (int i = 0; i < count; ++i) {
-        if (!gY[i] || !X[i] || !dW[i]) return PTV2_ERR_ARG;
-        m.gY[i] = gY[i]; m.X[i] = X[i]; m.dW[i] = dW[i]; m.db[i] = db ? db[i] : nullptr;
-        m.xsc[i] = xsc ? xsc[i] : nullptr;
-        m.xsh[i] = xsh ? xsh[i] : nullptr;
-        if ((m.xsc[i] == nullptr) != (m.xsh[i] == nullptr)) return PTV2_ERR_ARG;
-    }
-    float *part = (float *)workspace;
-    const int tiles_o = (cout + WG_TILE - 1) / WG_TILE, tiles_i = (cin + WG_TILE - 1) / WG_TILE;
-    dim3 grid(chunks, tiles_o * tiles_i, count);
-    {
-        // algorithmic bytes, strict: gY[i] once each, every DISTINCT X once (q, k, v share theirs), dW / db once each
-        int distinct_x = 0;
-        for (int i = 0; i < count; ++i) {
-            bool seen = false;
-            for (int j = 0; j < i; ++j) seen |= m.X[j] == m.X[i] && m.xsc[j] == m.xsc[i];
-            distinct_x += !seen;
-        }
-        bool lds_ok = !ptv2_matmul_bf16() && wgrad_lds_shape_ok(cout, cin);
-        for (int i = 0; i < count && lds_ok; ++i) lds_ok = wgrad_lds_ok(m.gY[i], cout, 0, m.X[i], cin, 0);
-        const double algo_bytes = 4.0 * ((double)count * n * cout + (double)distinct_x * n * cin + (double)count * cout * (cin + 1));
-        const int form = ptv2_matmul_bf16() ? 3 : (lds_ok ? 0 : 2);
-        if (g_wdefer.active && g_wdefer.armed && (int)g_wdefer.jobs[form].size() < WGRAD_MAX_JOBS) {
-            // inside a model backward: filed, and run with all the others by ONE launch at the end (WgradJob); the records go
-            // to the arena (the caller's workspace is reused before that launch)
-            float *keep = ptv2_wgrad_defer_alloc((size_t)chunks * rec);
-            if (keep) {
-                WgradJob J{};
-                J.n = n; J.cout = cout; J.cin = cin; J.tiles_i = tiles_i; J.tiles = tiles_o * tiles_i; J.batch = count;
-                J.chunk = chunk; J.chunks = chunks; J.has_pb = 1; J.count = count; J.rec = (int)rec;
-                J.wgs = chunks * J.tiles * J.batch;
-                J.ldy = cout; J.ldx = cin; J.part = keep;
-                for (int i = 0; i < count; ++i) {
-                    J.mgY[i] = m.gY[i]; J.mX[i] = m.X[i]; J.mxsc[i] = m.xsc[i]; J.mxsh[i] = m.xsh[i];
-                    J.mdW[i] = m.dW[i]; J.mdb[i] = m.db[i];
-                }
-                g_wdefer.jobs[form].push_back(J);
-                g_wdefer.bytes[form] += algo_bytes;
-                return PTV2_OK;
-            }
-        }
-        PtvScopedTimer t(lds_ok ? KID_WGRAD_LDS : KID_WGRAD, st, algo_bytes);
-        if (ptv2_matmul_bf16())
-            hipLaunchKernelGGL(linear_wgrad_kernel<true>, grid, dim3(TPB), 0, st, n, cout, cin, tiles_i, (const float *)nullptr,
-                               (long long)cout, 0LL, (const float *)nullptr, (long long)cin, 0LL, part, part, count, m, chunk);
-        else if (lds_ok) {
-            static const bool once = [] {
-                return hipFuncSetAttribute((const void *)linear_wgrad_lds_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)WL_LDS_BYTES) == hipSuccess;
-            }();
-            (void)once;
-            hipLaunchKernelGGL(linear_wgrad_lds_kernel<0>, grid, dim3(TPB), WL_LDS_BYTES, st, n, cout, cin, tiles_i,
-                               (const float *)nullptr, (long long)cout, 0LL, (const float *)nullptr, (long long)cin, 0LL, part, part,
-                               count, m, chunk, (const float *)nullptr, 0LL);
-        } else
-            hipLaunchKernelGGL(linear_wgrad_kernel<false>, grid, dim3(TPB), 0, st, n, cout, cin, tiles_i, (const float *)nullptr,
-                               (long long)cout, 0LL, (const float *)nullptr, (long long)cin, 0LL, part, part, count, m, chunk);
-    }
-    launch_finalize(st, (const float *)part, chunks, (int)rec, MapWgradMulti{m, cout * cin, cout});
-    PTV2_CHECK_LAUNCH();
-    return PTV2_OK;
+    const bool file = may_file(false);
+    WgradCall C;
+    const int prc = plan_multi(&C, n, cout, cin, count, gY, X, dW, db, xsc, xsh, file);
+    if (!workspace || workspace_bytes < sizeof(float) * (size_t)C.J.chunks * C.J.rec) return PTV2_ERR_WORKSPACE;
+    if (prc != PTV2_OK) return prc;
+    return wgrad_submit(C, file, workspace, workspace_bytes, stream);
 }
 
 extern "C" int linear_wgrad_hip_launcher(int n, int cout, int cin, const float *gY, const float *X, float *dW,

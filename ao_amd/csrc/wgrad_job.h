@@ -1,5 +1,7 @@
-// ao_amd/csrc/wgrad_job.h -- the record of a deferred weight-gradient launch (wgrad.hip: the launches of a whole backward
-// filed where they are called and run by one launch per kernel form at its end), shared with gva_wgrad_tile.hip.
+// ao_amd/csrc/wgrad_job.h -- one weight-gradient call as its kernels and its finalize read it (wgrad.hip plans it once per call;
+// launched at once it is the kernel's argument, by value; filed inside a model backward it is an entry of its kernel form's job
+// table, run by one launch per form at the backward's end), shared with gva_wgrad_tile.hip.  What only the host needs (form,
+// algorithmic bytes) stays out of it: eight of these are one 4 KB argument block of the table writer.
 #pragma once
 
 namespace dense {

@@ -420,6 +420,62 @@ def test_wgrad_cases_sit_on_the_chunk_rule():
     assert {c.count for c in R.WGRAD_CASES if c.kind == "strided"} == {1, 6, 48}
 
 
+# (route, batch, cout, cin, bf16 operands, weighted): the kernels linear_wgrad_strided_rowscale (ao_amd/csrc/internal.h; exported,
+# not in the public header) chooses between -- the grouped projection's vector-ALU kernel (cout = 8), the LDS-staged matrix-core
+# kernel with weighted bias sums, and the two that cannot form them (cin % 4 != 0: the direct fp32 kernel; bf16 operands)
+ROWSCALE_ROUTES = (("grouped", 6, 8, 48, False, 1), ("lds_rs", 2, 12, 48, False, 1), ("direct", 2, 8, 6, False, 0),
+                   ("bf16", 2, 12, 48, True, 0))
+
+
+def _rowscale_fn():
+    fn = _lib().lib().linear_wgrad_strided_rowscale
+    vp, ll = ctypes.c_void_p, ctypes.c_longlong
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int] * 4 + [vp, ll, ll, vp, ll, ll, vp, vp, vp, ll, ctypes.POINTER(ctypes.c_int), vp, ctypes.c_size_t, vp]
+    return fn
+
+
+@pytest.mark.parametrize("n", [1, 129, 1500])
+@pytest.mark.parametrize("route,batch,cout,cin,bf16,weighted", ROWSCALE_ROUTES, ids=[r[0] for r in ROWSCALE_ROUTES])
+def test_wgrad_rowscale_against_float64(route, batch, cout, cin, bf16, weighted, n):
+    """dW[b] = gY[:, b]^T X[:, b] and the WEIGHTED bias sums db[b][o] = sum_n gY[n, b, o] rowscale[n * lds_s + b], called as the
+    attention backward calls it (ldy = batch cout, ldx = batch cin, lds_s = batch).  Where the chosen kernel cannot form the
+    weighted sums *weighted is 0 and db is not written at all.  bf16 operands: dW to the margins of
+    tests/test_gpu_bf16.py::test_linear_wgrad_bf16_operands (5e-6 of the product of the rounded operands, 1e-2 of the fp32
+    statement's float64 value)."""
+    gen = torch.Generator().manual_seed(29 + n + 3 * cout + 5 * cin + batch)
+    gy, x, s = _rand(gen, n, batch * cout), _rand(gen, n, batch * cin), _rand(gen, n, batch)
+    nbytes = _size("dense_workspace_bytes", n, batch * cout, cin)
+    ws = _ws(nbytes)
+    got = dict(dW=_nan(batch, cout, cin), db=_nan(batch, cout))
+    flag = ctypes.c_int(-1)
+    L = _lib().lib()
+    prev = L.ptv2_matmul_precision(1) if bf16 else None
+    try:
+        rc = _rowscale_fn()(n, cout, cin, batch, _p(gy), batch * cout, cout, _p(x), batch * cin, cin, _p(got["dW"]), _p(got["db"]),
+                            _p(s), batch, ctypes.byref(flag), _p(ws), nbytes, _st())
+    finally:
+        if bf16:
+            L.ptv2_matmul_precision(prev)
+    assert rc == 0 and flag.value == weighted, (route, rc, flag.value)
+    ref, eager = {}, {}
+    for res, dt in ((ref, F64), (eager, F32)):
+        a, b = gy.to(dt).view(n, batch, cout), x.to(dt).view(n, batch, cin)
+        res["dW"], res["db"] = torch.einsum("nbo,nbi->boi", a, b), torch.einsum("nbo,nb->bo", a, s.to(dt))
+    torch.cuda.synchronize()
+    _ws_intact(ws, nbytes)
+    if not weighted:
+        assert bool(torch.isnan(got.pop("db")).all()), "db was written although *weighted is 0"
+        del ref["db"], eager["db"]
+    if bf16:
+        rounded = torch.einsum("nbo,nbi->boi", gy.bfloat16().double().view(n, batch, cout), x.bfloat16().double().view(n, batch, cin))
+        e_rounded, e_full = R.errors(got["dW"].double(), rounded)[0], R.errors(got["dW"].double(), ref["dW"])[0]
+        print("f64d rowscale-%s-n%d dW: %.3e of the rounded operands' product, %.3e of the float64 statement" % (route, n, e_rounded, e_full))
+        assert bool(torch.isfinite(got["dW"]).all()) and e_rounded < 5e-6 and e_full < 1e-2, (e_rounded, e_full)
+        return
+    compare("rowscale-%s-n%d" % (route, n), "default", got, ref, eager, set(ref))
+
+
 # -------------------------------------------------------------------------------------------------------------------- BatchNorm
 def _fin_forms(n, nrecs):
     return ("default", "nofin") if R.finapply_ok(n, nrecs) else ("default",)
