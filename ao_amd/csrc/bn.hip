@@ -11,6 +11,20 @@
 //                                  fixed-order final (bitwise reproducible); the finalizer also writes
 //                                  mean / rstd and updates the running statistics in place
 //   bn_apply / bn_backward_apply   one read-modify-write pass each
+// Where each thing is stated (once):
+//   bn_math.h        the per-element formulas, a float4 at a time: xhat, the forward affine and its ReLU / residual tails, the
+//                    two backward masks, the reduce step, the input gradient
+//   dense_common.h   BnTileSet (a forward fed from tile records), BnBwdSet (the operands of one backward), the tail of a
+//                    column-sum pass (column_sums_store), apply_grid
+//   here             bn_moments (mean / variance / rstd from the sums), bn_merge (one tile record into the running pair;
+//                    the loops around it keep their load batches and chains: the order of additions decides the bits),
+//                    bn_tiles_emit; the residual and plain routes are one kernel each, templated on RESIDUAL; the host
+//                    side has one reduce launch (bn_bwd_reduce) and one "records -> gx" tail (bn_bwd_finish) for the four
+//                    backward launchers, one bn_apply_launch and one bn_tiles_apply for the forward entry points.
+// The unit is compiled with the default contraction, and which products fuse depends on the shape of the code around them
+// (bn_bwd_apply_kernel loads dbeta / dgamma INSIDE its `if (training)`: with the loads selected against zero in front of the
+// branch the residual route's gx came out with other bits).  A change here is checked by comparing outputs bit for bit
+// against the build before it, not by reading the source.
 #include "dense_common.h"
 
 namespace dense {
@@ -36,21 +50,18 @@ __global__ __launch_bounds__(TPB) void bn_stats_kernel(int n, int c, const float
             s2.x = __builtin_fmaf(v.x, v.x, s2.x); s2.y = __builtin_fmaf(v.y, v.y, s2.y);
             s2.z = __builtin_fmaf(v.z, v.z, s2.z); s2.w = __builtin_fmaf(v.w, v.w, s2.w);
         }
-    float4 *sa = lds4, *sb = lds4 + TPB;
-    sa[threadIdx.x] = s1;
-    sb[threadIdx.x] = s2;
-    __syncthreads();
-    if (threadIdx.x < cq) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-        for (int k = 0; k < rl; ++k) {
-            const float4 u = sa[k * cq + threadIdx.x], w = sb[k * cq + threadIdx.x];
-            a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
-            b.x += w.x; b.y += w.y; b.z += w.z; b.w += w.w;
-        }
-        float *p = part + (size_t)blockIdx.x * 2 * c;
-        ((float4 *)p)[threadIdx.x] = a;
-        ((float4 *)(p + c))[threadIdx.x] = b;
-    }
+    column_sums_store(lds4, s1, s2, cq, rl, c, part + (size_t)blockIdx.x * 2 * c);
+}
+
+// mean, biased variance (clamped at 0) and rstd of n samples from their sum t1 and their sum of squares t2
+struct BnMoments { double mean, var; float rstd; };
+__device__ __forceinline__ BnMoments bn_moments(double t1, double t2, int n, float eps) {
+    BnMoments M;
+    M.mean = t1 / n;
+    const double var = t2 / n - M.mean * M.mean;
+    M.var = var > 0.0 ? var : 0.0;
+    M.rstd = (float)(1.0 / sqrt(M.var + (double)eps));
+    return M;
 }
 
 // finalize: column sums of (x-x0) and (x-x0)^2 over the per-block partials -> mean, rstd, running statistics
@@ -84,12 +95,10 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(
         double t1 = 0.0, t2 = 0.0;
 #pragma unroll 8
         for (int t = 0; t < SLICES; ++t) { t1 += s1[t][col]; t2 += s2[t][col]; }
-        const double d = t1 / n;                       // mean of the shifted samples
-        const double m = (double)x0[ch] + d;
-        double var = t2 / n - d * d;
-        var = var > 0.0 ? var : 0.0;
+        const BnMoments M = bn_moments(t1, t2, n, eps);  // of the shifted samples
+        const double m = (double)x0[ch] + M.mean, var = M.var;
         mean[ch] = (float)m;
-        rstd[ch] = (float)(1.0 / sqrt(var + (double)eps));
+        rstd[ch] = M.rstd;
         if (sc) {  // y = x * sc + sh is the whole normalisation: consumers apply it on their operand load
             const float scale = rstd[ch] * gamma[ch];
             sc[ch] = scale;
@@ -112,12 +121,22 @@ __device__ __forceinline__ int bn_tile_rows(const BnTileSet &S, int k, int n) { 
     return (n - k * rb) < rb ? (n - k * rb) : rb;
 }
 
+// one record (column sum s, centred sum of squares m2, cnt rows) into the running pair: a += S_b, b += M2_b + S_b^2 / n_b
+__device__ __forceinline__ void bn_merge(double &a, double &b, float s, float m2, int cnt) {
+    const double sb = (double)s;
+    a += sb;
+    b += (double)m2 + sb * sb / (double)cnt;
+}
+// the same for record k of S, column ch of c, loaded here
+__device__ __forceinline__ void bn_merge_record(const BnTileSet &S, int k, int n, int c, int ch, double &a, double &b) {
+    bn_merge(a, b, S.part[(size_t)k * 2 * c + ch], S.part[(size_t)k * 2 * c + c + ch], bn_tile_rows(S, k, n));
+}
+
 __device__ __forceinline__ void bn_tiles_emit(const BnTileSet &S, int ch, double t1, double t2, int n, float eps, float momentum) {
-    const double m = t1 / n;
-    double var = t2 / n - m * m;
-    var = var > 0.0 ? var : 0.0;
+    const BnMoments M = bn_moments(t1, t2, n, eps);
+    const double m = M.mean, var = M.var;
     S.mean[ch] = (float)m;
-    S.rstd[ch] = (float)(1.0 / sqrt(var + (double)eps));
+    S.rstd[ch] = M.rstd;
     if (S.sc) {
         const float scale = S.rstd[ch] * S.gamma[ch];
         S.sc[ch] = scale;
@@ -142,12 +161,6 @@ __global__ __launch_bounds__(1024) void bn_finalize_tiles_kernel(BnTileSet A, Bn
     const int ch = blockIdx.x * COLS + col;
     double a = 0.0, b = 0.0, a2 = 0.0, b2 = 0.0;
     if (ch < c) {
-        auto rec = [&](int k, double &sa, double &sq) {
-            const int cnt = bn_tile_rows(S, k, n);
-            const double sb = (double)part[(size_t)k * 2 * c + ch];
-            sa += sb;
-            sq += (double)part[(size_t)k * 2 * c + c + ch] + sb * sb / (double)cnt;
-        };
         int k = sl;
         // eight records (16 loads) in flight per trip, added in the order of the two-chain loop below (same bits): at the full
         // resolution (1 875 records, 3-6 workgroups) that loop was 15 dependent trips, 12.5 us on the critical path of every
@@ -161,18 +174,16 @@ __global__ __launch_bounds__(1024) void bn_finalize_tiles_kernel(BnTileSet A, Bn
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const int kk = k + u * SLICES;
-                const int cnt = bn_tile_rows(S, kk, n);
-                const double sb = (double)s[u];
-                if (u & 1) { a2 += sb; b2 += (double)m[u] + sb * sb / (double)cnt; }
-                else { a += sb; b += (double)m[u] + sb * sb / (double)cnt; }
+                const int cnt = bn_tile_rows(S, k + u * SLICES, n);
+                if (u & 1) bn_merge(a2, b2, s[u], m[u], cnt);
+                else bn_merge(a, b, s[u], m[u], cnt);
             }
         }
         for (; k + SLICES < nrb; k += 2 * SLICES) {  // two independent chains: the loads of both records are in flight
-            rec(k, a, b);
-            rec(k + SLICES, a2, b2);
+            bn_merge_record(S, k, n, c, ch, a, b);
+            bn_merge_record(S, k + SLICES, n, c, ch, a2, b2);
         }
-        for (; k < nrb; k += SLICES) rec(k, a, b);
+        for (; k < nrb; k += SLICES) bn_merge_record(S, k, n, c, ch, a, b);
     }
     s1[sl][col] = a + a2;
     s2[sl][col] = b + b2;
@@ -197,17 +208,11 @@ __global__ __launch_bounds__(1024) void bn_finalize_tiles_split_kernel(BnTileSet
     __shared__ double s1[SLICES][COLS], s2[SLICES][COLS];
     __shared__ int s_last;
     const BnTileSet &S = blockIdx.z ? B : A;
-    const float *__restrict__ part = S.part;
     const int col = threadIdx.x & (COLS - 1), sl = threadIdx.x / COLS;
     const int ch = blockIdx.x * COLS + col;
     double a = 0.0, b = 0.0;
     if (ch < c) {
-        for (int k = blockIdx.y * SLICES + sl; k < nrb; k += BNT_NS * SLICES) {
-            const int cnt = bn_tile_rows(S, k, n);
-            const double sb = (double)part[(size_t)k * 2 * c + ch];
-            a += sb;
-            b += (double)part[(size_t)k * 2 * c + c + ch] + sb * sb / (double)cnt;
-        }
+        for (int k = blockIdx.y * SLICES + sl; k < nrb; k += BNT_NS * SLICES) bn_merge_record(S, k, n, c, ch, a, b);
     }
     s1[sl][col] = a;
     s2[sl][col] = b;
@@ -243,213 +248,89 @@ __global__ __launch_bounds__(1024) void bn_finalize_tiles_split_kernel(BnTileSet
 }
 
 // ------------------------------------------------------------------ BN: apply --
+// y = BN(x), with the fused ReLU if `relu`.  RESIDUAL: the Block tail fused into the last BatchNorm of a Block
+// (point_transformer_v2m2_base.py:174-176):
+//   y = ReLU(residual + rowscale[n] * BN(x))      rowscale = per-point DropPath factor (0 or 1/keep), may be NULL
+template <bool RESIDUAL>
 __global__ __launch_bounds__(TPB) void bn_apply_kernel(long long total4, int cq, const float *__restrict__ x,
                                                        const float *__restrict__ mean, const float *__restrict__ rstd,
                                                        const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                       int relu, float *__restrict__ y) {
+                                                       int relu, const float *__restrict__ residual,
+                                                       const float *__restrict__ rowscale, float *__restrict__ y) {
     for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total4; e += (long long)gridDim.x * TPB) {
         const int q = (int)(e % cq);
-        const float4 v = ((const float4 *)x)[e];
-        const float4 m = ((const float4 *)mean)[q], r = ((const float4 *)rstd)[q];
-        const float4 g = ((const float4 *)gamma)[q], b = ((const float4 *)beta)[q];
-        float4 o;
-        o.x = __builtin_fmaf((v.x - m.x) * r.x, g.x, b.x);
-        o.y = __builtin_fmaf((v.y - m.y) * r.y, g.y, b.y);
-        o.z = __builtin_fmaf((v.z - m.z) * r.z, g.z, b.z);
-        o.w = __builtin_fmaf((v.w - m.w) * r.w, g.w, b.w);
-        if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-        ((float4 *)y)[e] = o;
+        const float4 h = bn_xhat(((const float4 *)x)[e], ((const float4 *)mean)[q], ((const float4 *)rstd)[q]);
+        const float4 o = bn_affine(h, ((const float4 *)gamma)[q], ((const float4 *)beta)[q]);
+        if (RESIDUAL) ((float4 *)y)[e] = bn_residual_relu(o, rowscale ? rowscale[e / cq] : 1.f, ((const float4 *)residual)[e]);
+        else ((float4 *)y)[e] = relu ? bn_relu(o) : o;
     }
 }
-
-// Block tail fused into the last BatchNorm of a Block (point_transformer_v2m2_base.py:174-176):
-//   y = ReLU(residual + rowscale[n] * BN(x))      rowscale = per-point DropPath factor (0 or 1/keep), may be NULL
-__global__ __launch_bounds__(TPB) void bn_apply_residual_kernel(long long total4, int cq, const float *__restrict__ x,
-                                                                const float *__restrict__ mean,
-                                                                const float *__restrict__ rstd,
-                                                                const float *__restrict__ gamma,
-                                                                const float *__restrict__ beta,
-                                                                const float *__restrict__ residual,
-                                                                const float *__restrict__ rowscale,
-                                                                float *__restrict__ y) {
-    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total4; e += (long long)gridDim.x * TPB) {
-        const int q = (int)(e % cq);
-        const float rsc = rowscale ? rowscale[e / cq] : 1.f;
-        const float4 v = ((const float4 *)x)[e], res = ((const float4 *)residual)[e];
-        const float4 m = ((const float4 *)mean)[q], r = ((const float4 *)rstd)[q];
-        const float4 g = ((const float4 *)gamma)[q], b = ((const float4 *)beta)[q];
-        float4 o;
-        o.x = fmaxf(__builtin_fmaf(rsc, __builtin_fmaf((v.x - m.x) * r.x, g.x, b.x), res.x), 0.f);
-        o.y = fmaxf(__builtin_fmaf(rsc, __builtin_fmaf((v.y - m.y) * r.y, g.y, b.y), res.y), 0.f);
-        o.z = fmaxf(__builtin_fmaf(rsc, __builtin_fmaf((v.z - m.z) * r.z, g.z, b.z), res.z), 0.f);
-        o.w = fmaxf(__builtin_fmaf(rsc, __builtin_fmaf((v.w - m.w) * r.w, g.w, b.w), res.w), 0.f);
-        ((float4 *)y)[e] = o;
-    }
-}
-
-// backward of the fused tail: d = gy * (y > 0) is the gradient of the residual; d * rowscale[n] enters the BN backward
-__global__ __launch_bounds__(TPB) void bn_bwd_reduce_residual_kernel(int n, int c, const float *__restrict__ x,
-                                                                     const float *__restrict__ gy,
-                                                                     const float *__restrict__ y,
-                                                                     const float *__restrict__ rowscale,
-                                                                     const float *__restrict__ mean,
-                                                                     const float *__restrict__ rstd,
-                                                                     float *__restrict__ part) {
-    extern __shared__ float4 lds4[];
-    const int cq = c >> 2;
-    const int rl = TPB / cq;
-    const int q = threadIdx.x % cq, r = threadIdx.x / cq;
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-    if (r < rl) {
-        const float4 m = ((const float4 *)mean)[q], rs = ((const float4 *)rstd)[q];
-#pragma unroll 4
-        for (long long row = (long long)blockIdx.x * rl + r; row < n; row += (long long)gridDim.x * rl) {
-            const float4 v = ((const float4 *)x)[row * cq + q], o = ((const float4 *)y)[row * cq + q];
-            float4 d = ((const float4 *)gy)[row * cq + q];
-            const float rsc = rowscale ? rowscale[row] : 1.f;
-            d.x = o.x > 0.f ? d.x * rsc : 0.f; d.y = o.y > 0.f ? d.y * rsc : 0.f;
-            d.z = o.z > 0.f ? d.z * rsc : 0.f; d.w = o.w > 0.f ? d.w * rsc : 0.f;
-            s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-            s2.x = __builtin_fmaf(d.x, (v.x - m.x) * rs.x, s2.x); s2.y = __builtin_fmaf(d.y, (v.y - m.y) * rs.y, s2.y);
-            s2.z = __builtin_fmaf(d.z, (v.z - m.z) * rs.z, s2.z); s2.w = __builtin_fmaf(d.w, (v.w - m.w) * rs.w, s2.w);
-        }
-    }
-    float4 *sa = lds4, *sb = lds4 + TPB;
-    sa[threadIdx.x] = s1;
-    sb[threadIdx.x] = s2;
-    __syncthreads();
-    if (threadIdx.x < cq) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b2 = a;
-        for (int k = 0; k < rl; ++k) {
-            const float4 u = sa[k * cq + threadIdx.x], w = sb[k * cq + threadIdx.x];
-            a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
-            b2.x += w.x; b2.y += w.y; b2.z += w.z; b2.w += w.w;
-        }
-        float *p = part + (size_t)blockIdx.x * 2 * c;
-        ((float4 *)p)[threadIdx.x] = a;
-        ((float4 *)(p + c))[threadIdx.x] = b2;
-    }
-}
-
-__global__ __launch_bounds__(TPB) void bn_bwd_apply_residual_kernel(
-    long long total4, int cq, float inv_n, const float *__restrict__ x, const float *__restrict__ gy,
-    const float *__restrict__ y, const float *__restrict__ rowscale, const float *__restrict__ mean,
-    const float *__restrict__ rstd, const float *__restrict__ gamma, const float *__restrict__ dbeta,
-    const float *__restrict__ dgamma, int training, float *__restrict__ gx, float *__restrict__ g_residual) {
-    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total4; e += (long long)gridDim.x * TPB) {
-        const int q = (int)(e % cq);
-        const float rsc = rowscale ? rowscale[e / cq] : 1.f;
-        const float4 v = ((const float4 *)x)[e], o = ((const float4 *)y)[e];
-        float4 d = ((const float4 *)gy)[e];
-        d.x = o.x > 0.f ? d.x : 0.f; d.y = o.y > 0.f ? d.y : 0.f; d.z = o.z > 0.f ? d.z : 0.f; d.w = o.w > 0.f ? d.w : 0.f;
-        ((float4 *)g_residual)[e] = d;
-        d.x *= rsc; d.y *= rsc; d.z *= rsc; d.w *= rsc;
-        const float4 m = ((const float4 *)mean)[q], rs = ((const float4 *)rstd)[q], g = ((const float4 *)gamma)[q];
-        float4 out;
-        if (training) {
-            const float4 db = ((const float4 *)dbeta)[q], dg = ((const float4 *)dgamma)[q];
-            out.x = g.x * rs.x * (d.x - db.x * inv_n - (v.x - m.x) * rs.x * dg.x * inv_n);
-            out.y = g.y * rs.y * (d.y - db.y * inv_n - (v.y - m.y) * rs.y * dg.y * inv_n);
-            out.z = g.z * rs.z * (d.z - db.z * inv_n - (v.z - m.z) * rs.z * dg.z * inv_n);
-            out.w = g.w * rs.w * (d.w - db.w * inv_n - (v.w - m.w) * rs.w * dg.w * inv_n);
-        } else {
-            out.x = g.x * rs.x * d.x; out.y = g.y * rs.y * d.y; out.z = g.z * rs.z * d.z; out.w = g.w * rs.w * d.w;
-        }
-        ((float4 *)gx)[e] = out;
-    }
-}
-
-// a second, independent BatchNorm of the same shape handled by blockIdx.y == 1 of the same launches (linear_q and
-// linear_k of a Block: their backward chains are independent, batching them saves three launches per Block)
-struct BnSecond {
-    const float *x, *gy, *mean, *rstd, *gamma, *beta;
-    float *gx, *dgamma, *dbeta;
-};
 
 // -------------------------------------------------------- BN: backward reduce --
-// partial columns [0,c): sum gy' ; [c,2c): sum gy' * xhat, with gy' = gy masked by the fused ReLU
-__global__ __launch_bounds__(TPB) void bn_bwd_reduce_kernel(int n, int c, const float *x, const float *gy,
-                                                            const float *mean, const float *rstd, const float *gamma,
-                                                            const float *beta, int relu, float *__restrict__ part,
-                                                            BnSecond second) {
+// partial columns [0,c): sum gy' ; [c,2c): sum gy' * xhat, with gy' = gy masked by the fused ReLU.  RESIDUAL, the backward of
+// the fused tail: gy' = gy * (y > 0) * rowscale[n] (gamma and beta are not read).  blockIdx.y == 1 works on A1, a second,
+// independent BatchNorm of the same shape in the same launch (linear_q and linear_k of a Block: their backward chains are
+// independent, batching them saves three launches per Block); record of a block: [set 0 | set 1]
+template <bool RESIDUAL>
+__global__ __launch_bounds__(TPB) void bn_bwd_reduce_kernel(int n, int c, int relu, float *__restrict__ part, BnBwdSet A0,
+                                                            BnBwdSet A1) {
     extern __shared__ float4 lds4[];
-    if (blockIdx.y) { x = second.x; gy = second.gy; mean = second.mean; rstd = second.rstd; gamma = second.gamma; beta = second.beta; }
+    const BnBwdSet &A = blockIdx.y ? A1 : A0;
     const int cq = c >> 2;
     const int rl = TPB / cq;
     const int q = threadIdx.x % cq, r = threadIdx.x / cq;
     float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
     if (r < rl) {
-        const float4 m = ((const float4 *)mean)[q], rs = ((const float4 *)rstd)[q];
-        const float4 g = ((const float4 *)gamma)[q], b = ((const float4 *)beta)[q];
+        const float4 m = ((const float4 *)A.mean)[q], rs = ((const float4 *)A.rstd)[q];
+        float4 g = s1, b = s1;
+        if (!RESIDUAL) { g = ((const float4 *)A.gamma)[q]; b = ((const float4 *)A.beta)[q]; }
 #pragma unroll 4
         for (long long row = (long long)blockIdx.x * rl + r; row < n; row += (long long)gridDim.x * rl) {
-            const float4 v = ((const float4 *)x)[row * cq + q];
-            float4 d = ((const float4 *)gy)[row * cq + q];
-            float4 h;
-            h.x = (v.x - m.x) * rs.x; h.y = (v.y - m.y) * rs.y; h.z = (v.z - m.z) * rs.z; h.w = (v.w - m.w) * rs.w;
-            if (relu) {
-                if (__builtin_fmaf(h.x, g.x, b.x) <= 0.f) d.x = 0.f;
-                if (__builtin_fmaf(h.y, g.y, b.y) <= 0.f) d.y = 0.f;
-                if (__builtin_fmaf(h.z, g.z, b.z) <= 0.f) d.z = 0.f;
-                if (__builtin_fmaf(h.w, g.w, b.w) <= 0.f) d.w = 0.f;
-            }
-            s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-            s2.x = __builtin_fmaf(d.x, h.x, s2.x); s2.y = __builtin_fmaf(d.y, h.y, s2.y);
-            s2.z = __builtin_fmaf(d.z, h.z, s2.z); s2.w = __builtin_fmaf(d.w, h.w, s2.w);
+            const float4 h = bn_xhat(((const float4 *)A.x)[row * cq + q], m, rs);
+            float4 d = ((const float4 *)A.gy)[row * cq + q];
+            if (RESIDUAL) d = bn_residual_mask(bn_scale(d, A.rowscale ? A.rowscale[row] : 1.f), ((const float4 *)A.y)[row * cq + q]);
+            else if (relu) d = bn_relu_mask(d, h, g, b);
+            bn_accumulate(s1, s2, d, h);
         }
     }
-    float4 *sa = lds4, *sb = lds4 + TPB;
-    sa[threadIdx.x] = s1;
-    sb[threadIdx.x] = s2;
-    __syncthreads();
-    if (threadIdx.x < cq) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b2 = a;
-        for (int k = 0; k < rl; ++k) {
-            const float4 u = sa[k * cq + threadIdx.x], w = sb[k * cq + threadIdx.x];
-            a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
-            b2.x += w.x; b2.y += w.y; b2.z += w.z; b2.w += w.w;
-        }
-        float *p = part + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 2 * c;  // record of a block: [set 0 | set 1]
-        ((float4 *)p)[threadIdx.x] = a;
-        ((float4 *)(p + c))[threadIdx.x] = b2;
-    }
+    column_sums_store(lds4, s1, s2, cq, rl, c, part + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 2 * c);
 }
 
-// gx = gamma * rstd * (gy' - dbeta/n - xhat * dgamma/n)   (training);   gamma * rstd * gy' (eval)
-__global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(long long total4, int cq, float inv_n, const float *x,
-                                                           const float *gy, const float *mean, const float *rstd,
-                                                           const float *gamma, const float *beta, int relu,
-                                                           const float *dbeta, const float *dgamma, int training, float *gx,
-                                                           BnSecond second) {
-    if (blockIdx.y) {
-        x = second.x; gy = second.gy; mean = second.mean; rstd = second.rstd; gamma = second.gamma; beta = second.beta;
-        dbeta = second.dbeta; dgamma = second.dgamma; gx = second.gx;
+// --------------------------------------------------------- BN: backward apply --
+// the gradient that enters the BatchNorm at float4 e of row `row`: gy masked by the fused ReLU; RESIDUAL: masked by y > 0 (that
+// is the residual's gradient, written here), then scaled by rowscale
+template <bool RESIDUAL>
+__device__ __forceinline__ float4 bn_bwd_masked(const BnBwdSet &A, long long e, long long row, const float4 h, const float4 g,
+                                                const float4 b, int relu) {
+    float4 d = ((const float4 *)A.gy)[e];
+    if (RESIDUAL) {
+        d = bn_residual_mask(d, ((const float4 *)A.y)[e]);
+        ((float4 *)A.g_residual)[e] = d;
+        d = bn_scale(d, A.rowscale ? A.rowscale[row] : 1.f);
+    } else if (relu) {
+        d = bn_relu_mask(d, h, g, b);
     }
+    return d;
+}
+
+// the pass over all elements, dbeta / dgamma finalized by the launch before; blockIdx.y selects the set as in the reduce
+template <bool RESIDUAL>
+__global__ __launch_bounds__(TPB) void bn_bwd_apply_kernel(long long total4, int cq, float inv_n, int relu, int training,
+                                                           BnBwdSet A0, BnBwdSet A1) {
+    const BnBwdSet &A = blockIdx.y ? A1 : A0;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total4; e += (long long)gridDim.x * TPB) {
         const int q = (int)(e % cq);
-        const float4 v = ((const float4 *)x)[e];
-        float4 d = ((const float4 *)gy)[e];
-        const float4 m = ((const float4 *)mean)[q], rs = ((const float4 *)rstd)[q];
-        const float4 g = ((const float4 *)gamma)[q], b = ((const float4 *)beta)[q];
-        float4 h;
-        h.x = (v.x - m.x) * rs.x; h.y = (v.y - m.y) * rs.y; h.z = (v.z - m.z) * rs.z; h.w = (v.w - m.w) * rs.w;
-        if (relu) {
-            if (__builtin_fmaf(h.x, g.x, b.x) <= 0.f) d.x = 0.f;
-            if (__builtin_fmaf(h.y, g.y, b.y) <= 0.f) d.y = 0.f;
-            if (__builtin_fmaf(h.z, g.z, b.z) <= 0.f) d.z = 0.f;
-            if (__builtin_fmaf(h.w, g.w, b.w) <= 0.f) d.w = 0.f;
-        }
-        float4 o;
+        const float4 m = ((const float4 *)A.mean)[q], rs = ((const float4 *)A.rstd)[q], g = ((const float4 *)A.gamma)[q];
+        const float4 b = RESIDUAL ? zero : ((const float4 *)A.beta)[q];
+        const float4 h = bn_xhat(((const float4 *)A.x)[e], m, rs);
+        const float4 d = bn_bwd_masked<RESIDUAL>(A, e, e / cq, h, g, b, relu);
         if (training) {
-            const float4 db = ((const float4 *)dbeta)[q], dg = ((const float4 *)dgamma)[q];
-            o.x = g.x * rs.x * (d.x - db.x * inv_n - h.x * dg.x * inv_n);
-            o.y = g.y * rs.y * (d.y - db.y * inv_n - h.y * dg.y * inv_n);
-            o.z = g.z * rs.z * (d.z - db.z * inv_n - h.z * dg.z * inv_n);
-            o.w = g.w * rs.w * (d.w - db.w * inv_n - h.w * dg.w * inv_n);
+            const float4 db = ((const float4 *)A.dbeta)[q], dg = ((const float4 *)A.dgamma)[q];
+            ((float4 *)A.gx)[e] = bn_gx(g, rs, d, db, dg, h, inv_n, 1);
         } else {
-            o.x = g.x * rs.x * d.x; o.y = g.y * rs.y * d.y; o.z = g.z * rs.z * d.z; o.w = g.w * rs.w * d.w;
+            ((float4 *)A.gx)[e] = bn_gx(g, rs, d, zero, zero, h, inv_n, 0);
         }
-        ((float4 *)gx)[e] = o;
     }
 }
 
@@ -483,20 +364,9 @@ __global__ __launch_bounds__(TPB) void bn_tiles_apply_residual_kernel(BnTileSet 
 #pragma unroll
                 for (int u = 0; u < 4; ++u) { sv[u] = p[(size_t)(k + u * SL) * 2 * c]; mv[u] = p[(size_t)(k + u * SL) * 2 * c + c]; }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int kk = k + u * SL;
-                    const int cnt = bn_tile_rows(S, kk, n);
-                    const double sb = (double)sv[u];
-                    a += sb;
-                    b += (double)mv[u] + sb * sb / (double)cnt;
-                }
+                for (int u = 0; u < 4; ++u) bn_merge(a, b, sv[u], mv[u], bn_tile_rows(S, k + u * SL, n));
             }
-            for (; k < nrb; k += SL) {
-                const int cnt = bn_tile_rows(S, k, n);
-                const double sb = (double)p[(size_t)k * 2 * c];
-                a += sb;
-                b += (double)p[(size_t)k * 2 * c + c] + sb * sb / (double)cnt;
-            }
+            for (; k < nrb; k += SL) bn_merge_record(S, k, n, c, col0 + cj, a, b);
         }
         s_a[sl][cj] = a;
         s_b[sl][cj] = b;
@@ -507,11 +377,9 @@ __global__ __launch_bounds__(TPB) void bn_tiles_apply_residual_kernel(BnTileSet 
         double t1 = 0.0, t2 = 0.0;
 #pragma unroll
         for (int t = 0; t < SL; ++t) { t1 += s_a[t][cj]; t2 += s_b[t][cj]; }
-        const double m = t1 / n;
-        double var = t2 / n - m * m;
-        var = var > 0.0 ? var : 0.0;
-        s_mean[cj] = (float)m;
-        s_rstd[cj] = (float)(1.0 / sqrt(var + (double)eps));
+        const BnMoments M = bn_moments(t1, t2, n, eps);
+        s_mean[cj] = (float)M.mean;
+        s_rstd[cj] = M.rstd;
         if (blockIdx.y == 0 && cj < ncol) bn_tiles_emit(S, col0 + cj, t1, t2, n, eps, momentum);
     }
     __syncthreads();
@@ -525,24 +393,9 @@ __global__ __launch_bounds__(TPB) void bn_tiles_apply_residual_kernel(BnTileSet 
     const long long r1 = (r0 + FA_ROWS) < (long long)n ? (r0 + FA_ROWS) : (long long)n;
     for (long long row = r0 + rl; row < r1; row += RL) {
         const long long e = row * cq + qcol;
-        if (PLAIN) {
-            const float4 v = ((const float4 *)x)[e];
-            float4 o;
-            o.x = fmaxf(__builtin_fmaf((v.x - m.x) * r.x, g.x, b.x), 0.f);
-            o.y = fmaxf(__builtin_fmaf((v.y - m.y) * r.y, g.y, b.y), 0.f);
-            o.z = fmaxf(__builtin_fmaf((v.z - m.z) * r.z, g.z, b.z), 0.f);
-            o.w = fmaxf(__builtin_fmaf((v.w - m.w) * r.w, g.w, b.w), 0.f);
-            ((float4 *)y)[e] = o;
-            continue;
-        }
-        const float rsc = rowscale ? rowscale[row] : 1.f;
-        const float4 v = ((const float4 *)x)[e], res = ((const float4 *)residual)[e];
-        float4 o;
-        o.x = fmaxf(__builtin_fmaf(rsc, __builtin_fmaf((v.x - m.x) * r.x, g.x, b.x), res.x), 0.f);
-        o.y = fmaxf(__builtin_fmaf(rsc, __builtin_fmaf((v.y - m.y) * r.y, g.y, b.y), res.y), 0.f);
-        o.z = fmaxf(__builtin_fmaf(rsc, __builtin_fmaf((v.z - m.z) * r.z, g.z, b.z), res.z), 0.f);
-        o.w = fmaxf(__builtin_fmaf(rsc, __builtin_fmaf((v.w - m.w) * r.w, g.w, b.w), res.w), 0.f);
-        ((float4 *)y)[e] = o;
+        const float4 o = bn_affine(bn_xhat(((const float4 *)x)[e], m, r), g, b);
+        if (PLAIN) ((float4 *)y)[e] = bn_relu(o);
+        else ((float4 *)y)[e] = bn_residual_relu(o, rowscale ? rowscale[row] : 1.f, ((const float4 *)residual)[e]);
     }
 }
 
@@ -556,18 +409,14 @@ __global__ __launch_bounds__(TPB) void bn_tiles_apply_residual_kernel(BnTileSet 
 // reproducible.  blockIdx.z selects one of two independent BatchNorms of the same shape (linear_q / linear_k).
 struct BnFinApply {
     const float *part; int nrec, rec_floats, off;   // record r, set columns: part[r * rec_floats + off + (0..c-1: dbeta, c..2c-1: dgamma)]
-    const float *x, *gy, *mean, *rstd, *gamma, *beta;
-    float *gx, *dbeta, *dgamma;
-    // residual tail (bn_backward_residual): the ReLU mask comes from y > 0, d * rowscale enters the BatchNorm, d itself is
-    // the residual gradient
-    const float *y, *rowscale;
-    float *g_residual;
+    BnBwdSet bn;
 };
 
 template <bool RESIDUAL>
 __global__ __launch_bounds__(TPB) void bn_bwd_finapply_kernel(int n, int c, int relu, int training, float inv_n, BnFinApply A0,
                                                               BnFinApply A1) {
     const BnFinApply &A = blockIdx.z ? A1 : A0;
+    const BnBwdSet &O = A.bn;
     constexpr int SL = TPB / (2 * FA_COLS);  // record slices
     __shared__ double s_part[SL][2 * FA_COLS];
     __shared__ __attribute__((aligned(16))) float s_db[FA_COLS], s_dg[FA_COLS];
@@ -600,47 +449,24 @@ __global__ __launch_bounds__(TPB) void bn_bwd_finapply_kernel(int n, int c, int 
         for (int u = 0; u < SL; ++u) t += s_part[u][j];
         const float v = (float)t;
         (which ? s_dg : s_db)[cj] = v;
-        if (blockIdx.y == 0 && cj < ncol) (which ? A.dgamma : A.dbeta)[col0 + cj] = v;
+        if (blockIdx.y == 0 && cj < ncol) (which ? O.dgamma : O.dbeta)[col0 + cj] = v;
     }
     __syncthreads();
     constexpr int QW = FA_COLS / 4, RL = TPB / QW;  // column quads of the stripe x row lanes
     const int cq = c >> 2, q = threadIdx.x % QW, rl = threadIdx.x / QW;
     const int qcol = (col0 >> 2) + q;
     if (4 * q >= ncol) return;
-    const float4 m = ((const float4 *)A.mean)[qcol], rs = ((const float4 *)A.rstd)[qcol], g = ((const float4 *)A.gamma)[qcol];
+    const float4 m = ((const float4 *)O.mean)[qcol], rs = ((const float4 *)O.rstd)[qcol], g = ((const float4 *)O.gamma)[qcol];
     float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!RESIDUAL && relu) b = ((const float4 *)A.beta)[qcol];
+    if (!RESIDUAL && relu) b = ((const float4 *)O.beta)[qcol];
     const float4 db = *(const float4 *)(s_db + 4 * q), dg = *(const float4 *)(s_dg + 4 * q);
     const long long r0 = (long long)blockIdx.y * FA_ROWS;
     const long long r1 = (r0 + FA_ROWS) < (long long)n ? (r0 + FA_ROWS) : (long long)n;
     for (long long row = r0 + rl; row < r1; row += RL) {
         const long long e = row * cq + qcol;
-        const float4 v = ((const float4 *)A.x)[e];
-        float4 d = ((const float4 *)A.gy)[e];
-        float4 h;
-        h.x = (v.x - m.x) * rs.x; h.y = (v.y - m.y) * rs.y; h.z = (v.z - m.z) * rs.z; h.w = (v.w - m.w) * rs.w;
-        if (RESIDUAL) {
-            const float4 o = ((const float4 *)A.y)[e];
-            const float rsc = A.rowscale ? A.rowscale[row] : 1.f;
-            d.x = o.x > 0.f ? d.x : 0.f; d.y = o.y > 0.f ? d.y : 0.f; d.z = o.z > 0.f ? d.z : 0.f; d.w = o.w > 0.f ? d.w : 0.f;
-            ((float4 *)A.g_residual)[e] = d;
-            d.x *= rsc; d.y *= rsc; d.z *= rsc; d.w *= rsc;
-        } else if (relu) {
-            if (__builtin_fmaf(h.x, g.x, b.x) <= 0.f) d.x = 0.f;
-            if (__builtin_fmaf(h.y, g.y, b.y) <= 0.f) d.y = 0.f;
-            if (__builtin_fmaf(h.z, g.z, b.z) <= 0.f) d.z = 0.f;
-            if (__builtin_fmaf(h.w, g.w, b.w) <= 0.f) d.w = 0.f;
-        }
-        float4 o;
-        if (training) {
-            o.x = g.x * rs.x * (d.x - db.x * inv_n - h.x * dg.x * inv_n);
-            o.y = g.y * rs.y * (d.y - db.y * inv_n - h.y * dg.y * inv_n);
-            o.z = g.z * rs.z * (d.z - db.z * inv_n - h.z * dg.z * inv_n);
-            o.w = g.w * rs.w * (d.w - db.w * inv_n - h.w * dg.w * inv_n);
-        } else {
-            o.x = g.x * rs.x * d.x; o.y = g.y * rs.y * d.y; o.z = g.z * rs.z * d.z; o.w = g.w * rs.w * d.w;
-        }
-        ((float4 *)A.gx)[e] = o;
+        const float4 h = bn_xhat(((const float4 *)O.x)[e], m, rs);
+        const float4 d = bn_bwd_masked<RESIDUAL>(O, e, row, h, g, b, relu);
+        ((float4 *)O.gx)[e] = bn_gx(g, rs, d, db, dg, h, inv_n, training);
     }
 }
 
@@ -651,15 +477,6 @@ static bool finapply_ok(int n, int nrec) {
     // (n <= 32768 -- the second level of the bench scene, 19 k rows -- measured the same step to 0.01 ms: the separate finalize +
     // apply pair stays there)
     return nrec <= 640 && n <= 16384 && !bn_finapply_off();  // (640: the 16-row records of the k-split GEMM at <= 10 k rows)
-}
-
-static void launch_finapply(hipStream_t st, int n, int c, int relu, int training, bool residual, int sets, const BnFinApply &A0,
-                            const BnFinApply &A1) {
-    const dim3 grid((unsigned)((c + FA_COLS - 1) / FA_COLS), (unsigned)((n + FA_ROWS - 1) / FA_ROWS), (unsigned)sets);
-    if (residual)
-        hipLaunchKernelGGL(bn_bwd_finapply_kernel<true>, grid, dim3(TPB), 0, st, n, c, relu, training, 1.0f / (float)n, A0, A1);
-    else
-        hipLaunchKernelGGL(bn_bwd_finapply_kernel<false>, grid, dim3(TPB), 0, st, n, c, relu, training, 1.0f / (float)n, A0, A1);
 }
 
 }  // namespace dense
@@ -713,18 +530,13 @@ __global__ __launch_bounds__(gva::FIN_COLS *gva::FIN_SLICES) void bn_fold_tiles_
                                                                                        int n) {
     __shared__ double s1[gva::FIN_SLICES][gva::FIN_COLS], s2[gva::FIN_SLICES][gva::FIN_COLS];
     const BnTileSet &S = blockIdx.z ? B : A;
-    const float *__restrict__ part = S.part;
     double *__restrict__ out = S.fold;
     const int col = threadIdx.x & (gva::FIN_COLS - 1), sl = threadIdx.x / gva::FIN_COLS;
     const int ch = blockIdx.x * gva::FIN_COLS + col;
     double a = 0.0, b = 0.0;
     if (ch < c) {
-        for (int k = blockIdx.y * gva::FIN_SLICES + sl; k < nrb; k += gridDim.y * gva::FIN_SLICES) {
-            const int cnt = bn_tile_rows(S, k, n);
-            const double sb = (double)part[(size_t)k * 2 * c + ch];
-            a += sb;
-            b += (double)part[(size_t)k * 2 * c + c + ch] + sb * sb / (double)cnt;
-        }
+        for (int k = blockIdx.y * gva::FIN_SLICES + sl; k < nrb; k += gridDim.y * gva::FIN_SLICES)
+            bn_merge_record(S, k, n, c, ch, a, b);
     }
     s1[sl][col] = a;
     s2[sl][col] = b;
@@ -820,51 +632,58 @@ int bn_tiles_finalize_pair(int n, int c, const BnTileSet (&sets)[2], float eps, 
     return bn_tiles_finalize_sets(n, c, 2, S, eps, momentum, stream, rb);
 }
 
-// internal (block.hip): BatchNorm statistics from the producing GEMM's tile records AND the Block tail
-// y = ReLU(residual + rowscale * BN(x)) in one launch when the records are few (deep levels); returns 0 when it declines
-int bn_tiles_apply_residual(int n, int c, const BnTileSet &S, float eps, float momentum, const float *x, const float *residual,
-                            const float *rowscale, float *y, void *stream) {
-    const int rb = S.rb;
-    const int nrb = (n + rb - 1) / rb;
-    if (nrb > (rb == 16 ? 512 : 256) || c % 4 != 0 || bn_finapply_off() || (rb != 16 && rb != 64)) return 0;
+// statistics from the producing launch's tile records and the apply pass in one launch when the records are few (at most
+// max_records); returns 0 when it declines
+static int bn_tiles_apply(int n, int c, const BnTileSet &S, int max_records, bool plain, float eps, float momentum, const float *x,
+                          const float *residual, const float *rowscale, float *y, hipStream_t st) {
+    const int nrb = (n + S.rb - 1) / S.rb;
+    if (nrb > max_records || c % 4 != 0 || bn_finapply_off()) return 0;
     const dim3 grid((unsigned)((c + FA_COLS - 1) / FA_COLS), (unsigned)((n + FA_ROWS - 1) / FA_ROWS));
-    {
-        PtvScopedTimer t(KID_BN_APPLY, (hipStream_t)stream, 12.0 * n * c);
-        hipLaunchKernelGGL(bn_tiles_apply_residual_kernel<0>, grid, dim3(TPB), 0, (hipStream_t)stream, S, nrb, n, c, eps, momentum, x,
-                           residual, rowscale, y);
-    }
+    PtvScopedTimer t(KID_BN_APPLY, st, (plain ? 8.0 : 12.0) * n * c);
+    if (plain)
+        hipLaunchKernelGGL(bn_tiles_apply_residual_kernel<1>, grid, dim3(TPB), 0, st, S, nrb, n, c, eps, momentum, x, residual, rowscale, y);
+    else
+        hipLaunchKernelGGL(bn_tiles_apply_residual_kernel<0>, grid, dim3(TPB), 0, st, S, nrb, n, c, eps, momentum, x, residual, rowscale, y);
     return 1;
 }
 
-// internal (model.hip): the same for y = ReLU(BN(x)) -- statistics from the producing GEMM's 64-row records and the apply pass in
-// one launch (was bn_stats + bn_finalize + bn_apply); returns 0 when it declines (many records: the three launches stay)
+// internal (block.hip): the Block tail y = ReLU(residual + rowscale * BN(x)) at the deep levels, records of 16 or 64 rows
+int bn_tiles_apply_residual(int n, int c, const BnTileSet &S, float eps, float momentum, const float *x, const float *residual,
+                            const float *rowscale, float *y, void *stream) {
+    if (S.rb != 16 && S.rb != 64) return 0;
+    return bn_tiles_apply(n, c, S, S.rb == 16 ? 512 : 256, false, eps, momentum, x, residual, rowscale, y, (hipStream_t)stream);
+}
+
+// internal (model.hip): the same for y = ReLU(BN(x)) from the producing GEMM's 64-row records (was bn_stats + bn_finalize +
+// bn_apply, which stay for many records)
 int bn_tiles_apply_relu(int n, int c, const BnTileSet &set, float eps, float momentum, const float *x, float *y, void *stream) {
-    const int nrb = (n + 63) / 64;
-    if (nrb > 512 || c % 4 != 0 || bn_finapply_off()) return 0;
     BnTileSet S = set;  // (no folded affine asked for; 64-row records)
     S.sc = S.sh = nullptr; S.rb = 64;
-    const dim3 grid((unsigned)((c + FA_COLS - 1) / FA_COLS), (unsigned)((n + FA_ROWS - 1) / FA_ROWS));
+    return bn_tiles_apply(n, c, S, 512, true, eps, momentum, x, nullptr, nullptr, y, (hipStream_t)stream);
+}
+
+// the apply pass; residual != NULL: the Block tail y = ReLU(residual + rowscale * BN(x))
+static int bn_apply_launch(int n, int c, const float *x, const float *mean, const float *rstd, const float *gamma,
+                           const float *beta, int relu, const float *residual, const float *rowscale, float *y, void *stream) {
+    if (n < 0 || c < 4 || c % 4 != 0) return PTV2_ERR_ARG;
+    if (n == 0) return PTV2_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const long long total4 = (long long)n * (c >> 2);
+    const dim3 grid(apply_grid(total4));
     {
-        PtvScopedTimer t(KID_BN_APPLY, (hipStream_t)stream, 8.0 * n * c);
-        hipLaunchKernelGGL(bn_tiles_apply_residual_kernel<1>, grid, dim3(TPB), 0, (hipStream_t)stream, S, nrb, n, c, eps, momentum, x,
-                           (const float *)nullptr, (const float *)nullptr, y);
+        PtvScopedTimer t(KID_BN_APPLY, st, (residual ? 12.0 : 8.0) * n * c);
+        if (residual)
+            hipLaunchKernelGGL(bn_apply_kernel<true>, grid, dim3(TPB), 0, st, total4, c >> 2, x, mean, rstd, gamma, beta, relu, residual, rowscale, y);
+        else
+            hipLaunchKernelGGL(bn_apply_kernel<false>, grid, dim3(TPB), 0, st, total4, c >> 2, x, mean, rstd, gamma, beta, relu, residual, rowscale, y);
     }
-    return 1;
+    PTV2_CHECK_LAUNCH();
+    return PTV2_OK;
 }
 
 extern "C" int bn_apply_hip_launcher(int n, int c, const float *x, const float *mean, const float *rstd,
                                      const float *gamma, const float *beta, int relu, float *y, void *stream) {
-    if (n < 0 || c < 4 || c % 4 != 0) return PTV2_ERR_ARG;
-    if (n == 0) return PTV2_OK;
-    const long long total4 = (long long)n * (c >> 2);
-    const int nblk = (int)std::min<long long>((total4 + TPB - 1) / TPB, 256 * 16);
-    {
-        PtvScopedTimer t(KID_BN_APPLY, (hipStream_t)stream, 8.0 * n * c);
-        hipLaunchKernelGGL(bn_apply_kernel, dim3(nblk), dim3(TPB), 0, (hipStream_t)stream, total4, c >> 2, x, mean, rstd,
-                           gamma, beta, relu, y);
-    }
-    PTV2_CHECK_LAUNCH();
-    return PTV2_OK;
+    return bn_apply_launch(n, c, x, mean, rstd, gamma, beta, relu, nullptr, nullptr, y, stream);
 }
 
 // training-mode forward as one call (statistics + running buffers, then the apply pass; residual != NULL selects
@@ -884,14 +703,58 @@ extern "C" int bn_forward_hip_launcher(int n, int c, const float *x, const float
 extern "C" int bn_apply_residual_hip_launcher(int n, int c, const float *x, const float *mean, const float *rstd,
                                               const float *gamma, const float *beta, const float *residual,
                                               const float *rowscale, float *y, void *stream) {
-    if (n < 0 || c < 4 || c % 4 != 0 || !residual) return PTV2_ERR_ARG;
-    if (n == 0) return PTV2_OK;
+    if (!residual) return PTV2_ERR_ARG;
+    return bn_apply_launch(n, c, x, mean, rstd, gamma, beta, 1, residual, rowscale, y, stream);
+}
+
+struct MapBnPair {  // record [dbeta0 c | dgamma0 c | dbeta1 c | dgamma1 c]
+    float *db0, *dg0, *db1, *dg1;
+    int c;
+    __device__ void operator()(int j, double v) const {
+        const int s = j / c, k = j - s * c;
+        (s == 0 ? db0 : s == 1 ? dg0 : s == 2 ? db1 : dg1)[k] = (float)v;
+    }
+};
+
+// A BatchNorm backward is the reduce pass below (or the records another launch left) and bn_bwd_finish.  `sets` (1 or 2)
+// BatchNorms of one shape share the launches: A[0 .. sets), record of a block [set 0: dbeta c | dgamma c][set 1: ...].  The
+// residual route (one set) masks by y > 0 and also writes g_residual.  Algorithmic bytes per n * c: 8 / 12 (residual) / 16
+// (pair) for the reduce, 12 / 20 / 24 for what follows.
+static void bn_bwd_reduce(hipStream_t st, int n, int c, int relu, bool residual, int sets, const BnBwdSet *A, float *part, int nblk) {
+    PtvScopedTimer t(KID_BN_BWD_REDUCE, st, (residual ? 12.0 : 8.0 * sets) * n * c);
+    const dim3 grid(nblk, sets);
+    const size_t lds = sizeof(float4) * 2 * TPB;
+    if (residual) hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, grid, dim3(TPB), lds, st, n, c, relu, part, A[0], A[sets - 1]);
+    else hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, dim3(TPB), lds, st, n, c, relu, part, A[0], A[sets - 1]);
+}
+
+// the nrec records are in `part`: the record sums inside the apply launch when they are few (finapply_ok), else finalize + apply
+static int bn_bwd_finish(hipStream_t st, int n, int c, int relu, int training, bool residual, int sets, const BnBwdSet *A,
+                         const float *part, int nrec) {
+    const int stride = sets * 2 * c;  // floats of a record
+    const double bytes = (residual ? 20.0 : 12.0 * sets) * n * c;
+    const float inv_n = 1.0f / (float)n;
+    if (finapply_ok(n, nrec)) {
+        PtvScopedTimer t(KID_BN_BWD_FINAPPLY, st, bytes);
+        BnFinApply F[2];
+        for (int i = 0; i < 2; ++i) {
+            const int set = i < sets ? i : sets - 1;
+            F[i].part = part; F[i].nrec = nrec; F[i].rec_floats = stride; F[i].off = set * 2 * c; F[i].bn = A[set];
+        }
+        const dim3 grid((unsigned)((c + FA_COLS - 1) / FA_COLS), (unsigned)((n + FA_ROWS - 1) / FA_ROWS), (unsigned)sets);
+        if (residual) hipLaunchKernelGGL(bn_bwd_finapply_kernel<true>, grid, dim3(TPB), 0, st, n, c, relu, training, inv_n, F[0], F[1]);
+        else hipLaunchKernelGGL(bn_bwd_finapply_kernel<false>, grid, dim3(TPB), 0, st, n, c, relu, training, inv_n, F[0], F[1]);
+        PTV2_CHECK_LAUNCH();
+        return PTV2_OK;
+    }
+    if (sets == 2) launch_finalize(st, part, nrec, stride, MapBnPair{A[0].dbeta, A[0].dgamma, A[1].dbeta, A[1].dgamma, c});
+    else launch_finalize(st, part, nrec, stride, gva::MapSplit2<float>{A[0].dbeta, A[0].dgamma, c});
     const long long total4 = (long long)n * (c >> 2);
-    const int nblk = (int)std::min<long long>((total4 + TPB - 1) / TPB, 256 * 16);
     {
-        PtvScopedTimer t(KID_BN_APPLY, (hipStream_t)stream, 12.0 * n * c);
-        hipLaunchKernelGGL(bn_apply_residual_kernel, dim3(nblk), dim3(TPB), 0, (hipStream_t)stream, total4, c >> 2, x, mean,
-                           rstd, gamma, beta, residual, rowscale, y);
+        PtvScopedTimer t(residual ? KID_BN_BWD_APPLY_RES : KID_BN_BWD_APPLY, st, bytes);
+        const dim3 grid(apply_grid(total4), sets);
+        if (residual) hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, grid, dim3(TPB), 0, st, total4, c >> 2, inv_n, relu, training, A[0], A[sets - 1]);
+        else hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(TPB), 0, st, total4, c >> 2, inv_n, relu, training, A[0], A[sets - 1]);
     }
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
@@ -907,28 +770,11 @@ extern "C" int bn_backward_residual_hip_launcher(int n, int c, const float *x, c
     hipStream_t st = (hipStream_t)stream;
     const int nblk = bn_grid(n, c);
     float *part = (float *)workspace;
-    {
-        PtvScopedTimer t(KID_BN_BWD_REDUCE, st, 12.0 * n * c);
-        hipLaunchKernelGGL(bn_bwd_reduce_residual_kernel, dim3(nblk), dim3(TPB), sizeof(float4) * 2 * TPB, st, n, c, x, gy, y,
-                           rowscale, mean, rstd, part);
-    }
-    if (finapply_ok(n, nblk)) {
-        PtvScopedTimer t(KID_BN_BWD_FINAPPLY, st, 20.0 * n * c);
-        const BnFinApply A{part, nblk, 2 * c, 0, x, gy, mean, rstd, gamma, nullptr, gx, dbeta, dgamma, y, rowscale, g_residual};
-        launch_finapply(st, n, c, 1, training, true, 1, A, A);
-        PTV2_CHECK_LAUNCH();
-        return PTV2_OK;
-    }
-    launch_finalize(st, (const float *)part, nblk, 2 * c, gva::MapSplit2<float>{dbeta, dgamma, c});
-    const long long total4 = (long long)n * (c >> 2);
-    const int nb2 = (int)std::min<long long>((total4 + TPB - 1) / TPB, 256 * 16);
-    {
-        PtvScopedTimer t(KID_BN_BWD_APPLY_RES, st, 20.0 * n * c);
-        hipLaunchKernelGGL(bn_bwd_apply_residual_kernel, dim3(nb2), dim3(TPB), 0, st, total4, c >> 2, 1.0f / (float)n, x, gy, y,
-                           rowscale, mean, rstd, gamma, (const float *)dbeta, (const float *)dgamma, training, gx, g_residual);
-    }
-    PTV2_CHECK_LAUNCH();
-    return PTV2_OK;
+    BnBwdSet A{};  // (beta stays NULL: the mask comes from y)
+    A.x = x; A.gy = gy; A.mean = mean; A.rstd = rstd; A.gamma = gamma; A.gx = gx; A.dbeta = dbeta; A.dgamma = dgamma;
+    A.y = y; A.rowscale = rowscale; A.g_residual = g_residual;
+    bn_bwd_reduce(st, n, c, 1, true, 1, &A, part, nblk);
+    return bn_bwd_finish(st, n, c, 1, training, true, 1, &A, part, nblk);
 }
 
 extern "C" int bn_backward_hip_launcher(int n, int c, const float *x, const float *gy, const float *mean,
@@ -940,28 +786,10 @@ extern "C" int bn_backward_hip_launcher(int n, int c, const float *x, const floa
     hipStream_t st = (hipStream_t)stream;
     const int nblk = bn_grid(n, c);
     float *part = (float *)workspace;
-    {
-        PtvScopedTimer t(KID_BN_BWD_REDUCE, st, 8.0 * n * c);
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(TPB), sizeof(float4) * 2 * TPB, st, n, c, x, gy, mean,
-                           rstd, gamma, beta, relu, part, BnSecond{});
-    }
-    if (finapply_ok(n, nblk)) {
-        PtvScopedTimer t(KID_BN_BWD_FINAPPLY, st, 12.0 * n * c);
-        const BnFinApply A{part, nblk, 2 * c, 0, x, gy, mean, rstd, gamma, beta, gx, dbeta, dgamma, nullptr, nullptr, nullptr};
-        launch_finapply(st, n, c, relu, training, false, 1, A, A);
-        PTV2_CHECK_LAUNCH();
-        return PTV2_OK;
-    }
-    launch_finalize(st, (const float *)part, nblk, 2 * c, gva::MapSplit2<float>{dbeta, dgamma, c});
-    const long long total4 = (long long)n * (c >> 2);
-    const int nb2 = (int)std::min<long long>((total4 + TPB - 1) / TPB, 256 * 16);
-    {
-        PtvScopedTimer t(KID_BN_BWD_APPLY, st, 12.0 * n * c);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nb2), dim3(TPB), 0, st, total4, c >> 2, 1.0f / (float)n, x, gy, mean,
-                           rstd, gamma, beta, relu, (const float *)dbeta, (const float *)dgamma, training, gx, BnSecond{});
-    }
-    PTV2_CHECK_LAUNCH();
-    return PTV2_OK;
+    BnBwdSet A{};
+    A.x = x; A.gy = gy; A.mean = mean; A.rstd = rstd; A.gamma = gamma; A.beta = beta; A.gx = gx; A.dbeta = dbeta; A.dgamma = dgamma;
+    bn_bwd_reduce(st, n, c, relu, false, 1, &A, part, nblk);
+    return bn_bwd_finish(st, n, c, relu, training, false, 1, &A, part, nblk);
 }
 
 // bn_backward whose reduce pass already ran in the epilogue of the GEMM that produced gy (rows_gemm_bnbwd_hip_launcher left
@@ -971,34 +799,10 @@ extern "C" int bn_backward_records_hip_launcher(int n, int c, const float *x, co
                                                 int training, float *gx, float *dgamma, float *dbeta, const float *records,
                                                 int nrec, void *stream) {
     if (n < 1 || c < 4 || c % 4 != 0 || c > 1024 || !records || nrec < 1) return PTV2_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (finapply_ok(n, nrec)) {
-        PtvScopedTimer t(KID_BN_BWD_FINAPPLY, st, 12.0 * n * c);
-        const BnFinApply A{records, nrec, 2 * c, 0, x, gy, mean, rstd, gamma, beta, gx, dbeta, dgamma, nullptr, nullptr, nullptr};
-        launch_finapply(st, n, c, relu, training, false, 1, A, A);
-        PTV2_CHECK_LAUNCH();
-        return PTV2_OK;
-    }
-    launch_finalize(st, records, nrec, 2 * c, gva::MapSplit2<float>{dbeta, dgamma, c});
-    const long long total4 = (long long)n * (c >> 2);
-    const int nb2 = (int)std::min<long long>((total4 + TPB - 1) / TPB, 256 * 16);
-    {
-        PtvScopedTimer t(KID_BN_BWD_APPLY, st, 12.0 * n * c);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nb2), dim3(TPB), 0, st, total4, c >> 2, 1.0f / (float)n, x, gy, mean,
-                           rstd, gamma, beta, relu, (const float *)dbeta, (const float *)dgamma, training, gx, BnSecond{});
-    }
-    PTV2_CHECK_LAUNCH();
-    return PTV2_OK;
+    BnBwdSet A{};
+    A.x = x; A.gy = gy; A.mean = mean; A.rstd = rstd; A.gamma = gamma; A.beta = beta; A.gx = gx; A.dbeta = dbeta; A.dgamma = dgamma;
+    return bn_bwd_finish((hipStream_t)stream, n, c, relu, training, false, 1, &A, records, nrec);
 }
-
-struct MapBnPair {  // record [dbeta0 c | dgamma0 c | dbeta1 c | dgamma1 c]
-    float *db0, *dg0, *db1, *dg1;
-    int c;
-    __device__ void operator()(int j, double v) const {
-        const int s = j / c, k = j - s * c;
-        (s == 0 ? db0 : s == 1 ? dg0 : s == 2 ? db1 : dg1)[k] = (float)v;
-    }
-};
 
 // two BatchNorm backwards of one shape (x[i], gy[i], ... i = 0, 1) in the three launches of one
 // (workspace: dense_workspace_bytes(n, 2 * c, c))
@@ -1016,31 +820,12 @@ extern "C" int bn_backward_pair_hip_launcher(int n, int c, const float *const *x
     const int left = ptv2_skinny_bn_take_records(n, c, part, gy);  // records of the launch that formed gy (skinny.hip), if any
     const bool reduced = left > 0;
     if (reduced) nblk = left;
-    const BnSecond sec{x[1], gy[1], mean[1], rstd[1], gamma[1], beta[1], gx[1], dgamma[1], dbeta[1]};
-    if (!reduced) {  // (else: the records are there already, left by the launch that formed gy -- skinny_backward_pair_bn_reduce)
-        PtvScopedTimer t(KID_BN_BWD_REDUCE, st, 16.0 * n * c);
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk, 2), dim3(TPB), sizeof(float4) * 2 * TPB, st, n, c, x[0], gy[0], mean[0],
-                           rstd[0], gamma[0], beta[0], relu, part, sec);
+    BnBwdSet A[2] = {};
+    for (int i = 0; i < 2; ++i) {
+        A[i].x = x[i]; A[i].gy = gy[i]; A[i].mean = mean[i]; A[i].rstd = rstd[i]; A[i].gamma = gamma[i]; A[i].beta = beta[i];
+        A[i].gx = gx[i]; A[i].dbeta = dbeta[i]; A[i].dgamma = dgamma[i];
     }
-    if (finapply_ok(n, nblk)) {  // record of a block: [set 0: dbeta c | dgamma c][set 1: ...]
-        PtvScopedTimer t(KID_BN_BWD_FINAPPLY, st, 24.0 * n * c);
-        const BnFinApply A0{part, nblk, 4 * c, 0, x[0], gy[0], mean[0], rstd[0], gamma[0], beta[0], gx[0], dbeta[0], dgamma[0], nullptr,
-                            nullptr, nullptr};
-        const BnFinApply A1{part, nblk, 4 * c, 2 * c, x[1], gy[1], mean[1], rstd[1], gamma[1], beta[1], gx[1], dbeta[1], dgamma[1],
-                            nullptr, nullptr, nullptr};
-        launch_finapply(st, n, c, relu, training, false, 2, A0, A1);
-        PTV2_CHECK_LAUNCH();
-        return PTV2_OK;
-    }
-    launch_finalize(st, (const float *)part, nblk, 4 * c, MapBnPair{dbeta[0], dgamma[0], dbeta[1], dgamma[1], c});
-    const long long total4 = (long long)n * (c >> 2);
-    const int nb2 = (int)std::min<long long>((total4 + TPB - 1) / TPB, 256 * 16);
-    {
-        PtvScopedTimer t(KID_BN_BWD_APPLY, st, 24.0 * n * c);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nb2, 2), dim3(TPB), 0, st, total4, c >> 2, 1.0f / (float)n, x[0], gy[0],
-                           mean[0], rstd[0], gamma[0], beta[0], relu, (const float *)dbeta[0], (const float *)dgamma[0], training,
-                           gx[0], sec);
-    }
-    PTV2_CHECK_LAUNCH();
-    return PTV2_OK;
+    // (reduced: the records are there already, left by the launch that formed gy -- skinny_backward_pair_bn_reduce)
+    if (!reduced) bn_bwd_reduce(st, n, c, relu, false, 2, A, part, nblk);
+    return bn_bwd_finish(st, n, c, relu, training, false, 2, A, part, nblk);
 }

@@ -161,34 +161,12 @@ __global__ __launch_bounds__(TPB) void skinny_bn_bwd_reduce_kernel(int n, int c,
                 d.z = __builtin_fmaf(sv, w.z, d.z); d.w = __builtin_fmaf(sv, w.w, d.w);
             }
             ((float4 *)S.gy)[row * cq + q] = d;
-            float4 h;
-            h.x = (v.x - m.x) * rs.x; h.y = (v.y - m.y) * rs.y; h.z = (v.z - m.z) * rs.z; h.w = (v.w - m.w) * rs.w;
-            if (relu) {
-                if (__builtin_fmaf(h.x, g.x, b.x) <= 0.f) d.x = 0.f;
-                if (__builtin_fmaf(h.y, g.y, b.y) <= 0.f) d.y = 0.f;
-                if (__builtin_fmaf(h.z, g.z, b.z) <= 0.f) d.z = 0.f;
-                if (__builtin_fmaf(h.w, g.w, b.w) <= 0.f) d.w = 0.f;
-            }
-            s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-            s2.x = __builtin_fmaf(d.x, h.x, s2.x); s2.y = __builtin_fmaf(d.y, h.y, s2.y);
-            s2.z = __builtin_fmaf(d.z, h.z, s2.z); s2.w = __builtin_fmaf(d.w, h.w, s2.w);
+            const float4 h = bn_xhat(v, m, rs);
+            if (relu) d = bn_relu_mask(d, h, g, b);
+            bn_accumulate(s1, s2, d, h);
         }
     }
-    float4 *sa = lds4, *sb = lds4 + TPB;
-    sa[threadIdx.x] = s1;
-    sb[threadIdx.x] = s2;
-    __syncthreads();
-    if (threadIdx.x < cq) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b2 = a;
-        for (int k = 0; k < rl; ++k) {
-            const float4 u = sa[k * cq + threadIdx.x], w = sb[k * cq + threadIdx.x];
-            a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
-            b2.x += w.x; b2.y += w.y; b2.z += w.z; b2.w += w.w;
-        }
-        float *p = part + ((size_t)blockIdx.x * 2 + blockIdx.y) * 2 * c;  // record of a block: [set 0 | set 1]
-        ((float4 *)p)[threadIdx.x] = a;
-        ((float4 *)(p + c))[threadIdx.x] = b2;
-    }
+    column_sums_store(lds4, s1, s2, cq, rl, c, part + ((size_t)blockIdx.x * 2 + blockIdx.y) * 2 * c);  // record of a block: [set 0 | set 1]
 }
 
 }  // namespace dense
@@ -245,7 +223,7 @@ extern "C" int skinny_linear_backward_hip_launcher(int n, int cin, int cout, con
     if (n < 0 || cin < 4 || cin % 4 != 0 || cout < 1) return PTV2_ERR_ARG;
     if (n == 0) return PTV2_OK;
     const long long total = (long long)n * (cin >> 2);
-    const int nblk = (int)std::min<long long>((total + TPB - 1) / TPB, 256 * 16);
+    const int nblk = apply_grid(total);
     {
         PtvScopedTimer t(KID_SKINNY_BWD, (hipStream_t)stream, 4.0 * n * (cin + cout));
         hipLaunchKernelGGL(skinny_bwd_kernel, dim3(nblk), dim3(TPB), 0, (hipStream_t)stream, (long long)n, cin, cout, gy, W, gx,
@@ -260,7 +238,7 @@ int skinny_linear_backward_pair(int n, int cin, int cout, const float *const *gy
     if (n < 0 || cin < 4 || cin % 4 != 0 || cout < 1) return PTV2_ERR_ARG;
     if (n == 0) return PTV2_OK;
     const long long total = (long long)n * (cin >> 2);
-    const int nblk = (int)std::min<long long>((total + TPB - 1) / TPB, 256 * 16);
+    const int nblk = apply_grid(total);
     {
         PtvScopedTimer t(KID_SKINNY_BWD, (hipStream_t)stream, 8.0 * n * (cin + cout));
         // the parameter-gradient sums queued by the stages before (logits parameters, kW / qW weights) ride along: gx

@@ -208,6 +208,7 @@ BN_N = (1, 2, 3, 63, 64, 65, 127, 128, 129, 1074, 4501, 16384, 16385, 18905, 120
 BN_C = (4, 8, 48, 96, 192, 384, 512, 1024)
 BN_GRID_EDGE = (63 * 84, 63 * 84 + 1, 64 * 84 + 1)      # bn_grid(n, 48) = 63 / 64 / 65 records (21 row lanes x 4 rows each)
 BN_REC_EDGE = (640 * 16, 640 * 16 + 1)                  # 640 / 641 records of 16 rows: finapply_ok's record limit
+BN_FOLD_N = 4096 * 64 + 1                               # 4097 records of 64 rows: bn_tiles_finalize folds in two levels
 
 
 def _bn_cases():
@@ -229,6 +230,7 @@ def _bn_cases():
         add(n, 48, "const")      # stats with a constant column (var = 0, rstd = eps^-1/2)
     for n in BN_REC_EDGE:
         add(n, 48, "records16")
+    add(BN_FOLD_N, 8, "fold")
     return out
 
 

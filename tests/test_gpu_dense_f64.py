@@ -489,6 +489,8 @@ def _bn_pairs():
                       ("residual", R.bn_grid(case.n, case.c)), ("records", R.nrec(case.n)))
         elif case.kind == "records16":
             groups = (("records16", R.nrec(case.n, 16)),)
+        elif case.kind == "fold":
+            groups = (("tiles", None),)
         else:
             groups = (("stats", None), ("forward", None), ("tiles", None)) if case.kind == "stats" else (("stats", None),)
         for group, nrecs in groups:
@@ -670,15 +672,22 @@ def bn_stats_check(case, group):
             assert int(nbt) == 42
     else:   # tiles: the statistics records of rows_gemm_fused merged by bn_tiles_finalize
         k = 48
-        xg, w, b = _rand(gen, n, k), _rand(gen, c, k, scale=k ** -0.5), _rand(gen, c, scale=3.0)
-        h = _nan(n, c)
         floats = _size("bn_tiles_floats", n, c)
         part = _records(floats)
-        _call("rows_gemm_fused_hip_launcher", n, c, k, 1, 0, _arr([xg]), _arr([w]), 0, _arr([b]), _arr([h]), 0, 0, 0, _arr([part]), _st())
+        if case.kind == "fold":   # more than 4096 records (two-level fold): the 64-row records of x, made in float64, rounded to fp32
+            s, m2, _ = R.stats_records(x.double())
+            assert s.shape[0] == R.nrec(n) > 4096
+            part[: s.shape[0] * 2 * c] = torch.stack([s, m2], 1).float().flatten()
+            made = lambda dt: x
+        else:
+            xg, w, b = _rand(gen, n, k), _rand(gen, c, k, scale=k ** -0.5), _rand(gen, c, scale=3.0)
+            h = _nan(n, c)
+            _call("rows_gemm_fused_hip_launcher", n, c, k, 1, 0, _arr([xg]), _arr([w]), 0, _arr([b]), _arr([h]), 0, 0, 0, _arr([part]), _st())
+            made = lambda dt: R.gemm([xg], [w], 0, bias=b, dtype=dt)
         o, nbt = fresh()
         _call("bn_tiles_finalize_hip_launcher", n, c, _p(part), _p(gamma), _p(beta), _p(o["mean"]), _p(o["rstd"]), _p(o["sc"]),
               _p(o["sh"]), _p(o["run_mean"]), _p(o["run_var"]), _p(nbt), R.EPS, R.MOMENTUM, _st())
-        ref, eager = (R.bn_stats(R.gemm([xg], [w], 0, bias=b, dtype=dt), gamma, beta, rm0, rv0, dtype=dt) for dt in (F64, F32))
+        ref, eager = (R.bn_stats(made(dt), gamma, beta, rm0, rv0, dtype=dt) for dt in (F64, F32))
         compare(case.name, "tiles", o, ref, eager, STATS_KEYS + ("sc", "sh"))
         assert int(nbt) == 42
         torch.cuda.synchronize()
@@ -705,6 +714,7 @@ def test_batchnorm_against_float64(case, group, form, monkeypatch):
 def test_batchnorm_cases_sit_on_the_dispatch_edges():
     assert [R.bn_grid(n, 48) for n in R.BN_GRID_EDGE] == [63, 64, 65]
     assert [R.nrec(n, 16) for n in R.BN_REC_EDGE] == [640, 641]
+    assert R.nrec(R.BN_FOLD_N) == 4097 and any(c.kind == "fold" and c.n == R.BN_FOLD_N for c in R.BN_CASES)
     assert R.finapply_ok(R.BN_REC_EDGE[0], 640) and not R.finapply_ok(R.BN_REC_EDGE[1], 641)
     assert R.finapply_ok(16384, R.bn_grid(16384, 48)) and not R.finapply_ok(16385, R.bn_grid(16385, 48))
     assert R.bn_grid(16384, 48) == 128 and R.bn_grid(120000, 48) == 512
