@@ -128,3 +128,10 @@ if not os.path.exists(PP2S_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % PP2S_HEADER)
 with open(PP2S_HEADER) as _f:
     pp2s_consts, pp2s_structs, pp2s_signatures = parse(_f.read())
+
+# the fifth public header (Point Transformer V1's vector-attention layer), likewise
+PTV1_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_ptv1_hip.h")
+if not os.path.exists(PTV1_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % PTV1_HEADER)
+with open(PTV1_HEADER) as _f:
+    ptv1_consts, ptv1_structs, ptv1_signatures = parse(_f.read())

@@ -32,6 +32,8 @@ EXPECTED_DATA_ABI = 1
 EXPECTED_REFINE_ABI = 1
 # the same for include/ptv2_pp2s_hip.h and ptv2_pp2s_abi_version() (ao_amd/csrc/pp2s.hip)
 EXPECTED_PP2S_ABI = 1
+# the same for include/ptv2_ptv1_hip.h and ptv2_ptv1_abi_version() (ao_amd/csrc/ptv1.hip)
+EXPECTED_PTV1_ABI = 1
 
 
 def build(verbose=False):
@@ -49,7 +51,8 @@ def lib():
                 "ao_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C ao_amd/csrc` (needs hipcc). There is no CPU fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures, _abi.pp2s_signatures):
+        for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures, _abi.pp2s_signatures,
+                      _abi.ptv1_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -74,6 +77,14 @@ def lib():
         if have != EXPECTED_PP2S_ABI:
             raise RuntimeError("ao_amd: %s has pp2s ABI version %d, the python side expects %d -- stale build; rebuild with "
                                "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_PP2S_ABI))
+        have = handle.ptv2_ptv1_abi_version()
+        if have != EXPECTED_PTV1_ABI:
+            raise RuntimeError("ao_amd: %s has ptv1 ABI version %d, the python side expects %d -- stale build; rebuild with "
+                               "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_PTV1_ABI))
+        for which, name in enumerate(("ptv1_params", "ptv1_norms", "ptv1_grads")):
+            if handle.ptv2_ptv1_struct_bytes(which) != ctypes.sizeof(_abi.ptv1_structs[name]):
+                raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (
+                    name, ctypes.sizeof(_abi.ptv1_structs[name]), handle.ptv2_ptv1_struct_bytes(which), LIB_PATH))
         for which, name in enumerate(("ptv2_aug_step", "ptv2_aug_program")):
             if handle.ptv2_data_struct_bytes(which) != ctypes.sizeof(_abi.data_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

@@ -33,7 +33,8 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
     segmentor and `Criteria` then builds it from the same config entry; with TEST (pointcept/engines/test.py:26) the whole-scene
     tester of ao_amd/ptv2/tester.py under "SemSegTester", which `test = dict(type="SemSegTester")` then resolves to.  Every
     registry may be omitted.  MODELS also receives
-    CACSegmentor under "CAC-v1m1"; the returned list of names leaves that entry out (it predates it)."""
+    CACSegmentor under "CAC-v1m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50"; the returned
+    list of names leaves those entries out (it predates them)."""
     done = []
     if MODELS is not None:
         from .model import PointTransformerV2
@@ -46,6 +47,12 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
             done.append(name)
         # (filed under MODELS as well, but not listed in the return value: callers compare that list with the names above)
         _register(MODELS, CACSegmentor, "CAC-v1m1", force)
+        # Point Transformer V1 (ao_amd/ptv1), likewise filed and not listed
+        from ..ptv1 import PointTransformerSeg26, PointTransformerSeg38, PointTransformerSeg50
+
+        for cls, name in ((PointTransformerSeg26, "PointTransformer-Seg26"), (PointTransformerSeg38, "PointTransformer-Seg38"),
+                          (PointTransformerSeg50, "PointTransformer-Seg50")):
+            _register(MODELS, cls, name, force)
     if OPTIMIZERS is not None:
         from .optim import FlatAdamW
 
