@@ -135,3 +135,10 @@ if not os.path.exists(PTV1_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % PTV1_HEADER)
 with open(PTV1_HEADER) as _f:
     ptv1_consts, ptv1_structs, ptv1_signatures = parse(_f.read())
+
+# the sixth public header (SpUNet-v1m1's sparse convolutions and their tables), likewise
+SPCONV_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_spconv_hip.h")
+if not os.path.exists(SPCONV_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SPCONV_HEADER)
+with open(SPCONV_HEADER) as _f:
+    spconv_consts, spconv_structs, spconv_signatures = parse(_f.read())

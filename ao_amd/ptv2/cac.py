@@ -183,11 +183,11 @@ def _soft_protos_torch(x, logits, bounds, thr):
 
 def _class_means_torch(x, label, k):
     """(means (K, C), present (K,)) of the rows with a label in [0, K)."""
-    valid = (label >= 0) & (label < k)
-    y = torch.where(valid, label, torch.zeros_like(label))
-    w = valid.float()
-    cnt = torch.zeros(k, dtype=torch.float32, device=x.device).index_add(0, y, w)
-    sums = torch.zeros((k, x.shape[1]), dtype=torch.float32, device=x.device).index_add(0, y, x.float() * w[:, None])
+    # a one-hot product, not index_add: on the device that adds with float atomics, and two identical steps then differ in the
+    # last place (a label outside [0, K) matches no column)
+    hot = (label.unsqueeze(1) == torch.arange(k, device=label.device).unsqueeze(0)).float()
+    cnt = hot.sum(0)
+    sums = hot.t() @ x.float()
     return sums / (cnt + MEAN_EPS)[:, None], cnt > 0
 
 
