@@ -142,3 +142,10 @@ if not os.path.exists(SPCONV_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SPCONV_HEADER)
 with open(SPCONV_HEADER) as _f:
     spconv_consts, spconv_structs, spconv_signatures = parse(_f.read())
+
+# the seventh public header (PointGroup's clustering stage: ball query, clusters, proposals, offset losses), likewise
+PG_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_pg_hip.h")
+if not os.path.exists(PG_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % PG_HEADER)
+with open(PG_HEADER) as _f:
+    pg_consts, pg_structs, pg_signatures = parse(_f.read())

@@ -33,7 +33,7 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
     segmentor and `Criteria` then builds it from the same config entry; with TEST (pointcept/engines/test.py:26) the whole-scene
     tester of ao_amd/ptv2/tester.py under "SemSegTester", which `test = dict(type="SemSegTester")` then resolves to.  Every
     registry may be omitted.  MODELS also receives
-    CACSegmentor under "CAC-v1m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50" and SpUNetBase under "SpUNet-v1m1"; the returned
+    CACSegmentor under "CAC-v1m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1" and PointGroup under "PG-v1m1"; the returned
     list of names leaves those entries out (it predates them)."""
     done = []
     if MODELS is not None:
@@ -57,6 +57,10 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
         from ..spunet import SpUNetBase
 
         _register(MODELS, SpUNetBase, "SpUNet-v1m1", force)
+        # PointGroup (ao_amd/pointgroup), likewise filed and not listed
+        from ..pointgroup import PointGroup
+
+        _register(MODELS, PointGroup, "PG-v1m1", force)
     if OPTIMIZERS is not None:
         from .optim import FlatAdamW
 

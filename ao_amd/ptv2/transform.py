@@ -35,8 +35,10 @@ point index and the step's stream number) or from a `noise=` tensor.
 
 Not here, on purpose: RandomDropout, HueSaturationTranslation, RandomColorJitter / RandomColorGrayScale (commented out in
 every PT-v2m2 config, or active only in one ScanNet list with a ratio the data-efficient benchmarks use), NormalizeCoord,
-PositiveShift, CropBoundary and the contrastive / instance transforms (ContrastiveViewsGenerator, InstanceParser), which
-belong to other model families.
+PositiveShift, CropBoundary and the contrastive transforms (ContrastiveViewsGenerator), which belong to other model families.
+
+InstanceParser (:1071-1104) is here for PointGroup (ao_amd/pointgroup): torch segment reductions on whatever device the data
+is on instead of the reference's loop over the instances.
 """
 import copy
 import ctypes
@@ -266,6 +268,40 @@ class NormalizeColor:
             # (a tensor divisor: with a python scalar torch multiplies by the rounded reciprocal on the GPU, 1 ulp off
             # numpy's IEEE division)
             data_dict["color"] = color / torch.full((1,), 127.5, dtype=color.dtype, device=color.device) - 1
+        return data_dict
+
+
+class InstanceParser:
+    """`instance` renumbered 0 .. I - 1 in ascending order of the original ids over the points whose `segment` is not ignored
+    (the others get instance_ignore_index); `instance_center` (n, 3): the mean coordinate of a point's instance, the ignore
+    value on ignored rows; `bbox` (I, 6): minimum and maximum coordinate per instance.  The mean is summed in float64 and
+    returned in coord's dtype (the reference sums fp32 and stores into a float64 array)."""
+
+    def __init__(self, segment_ignore_index=(-1, 0, 1), instance_ignore_index=-1):
+        self.segment_ignore_index = segment_ignore_index
+        self.instance_ignore_index = instance_ignore_index
+
+    def __call__(self, data_dict):
+        coord, segment, instance = data_dict["coord"], data_dict["segment"], data_dict["instance"]
+        mask = torch.ones_like(segment, dtype=torch.bool)
+        for index in self.segment_ignore_index:
+            mask &= segment != index
+        unique, inverse = torch.unique(instance[mask], return_inverse=True)
+        count = unique.numel()
+        instance = torch.full_like(instance, self.instance_ignore_index)
+        instance[mask] = inverse.to(instance.dtype)
+        kept = coord[mask]
+        rows = inverse[:, None].expand(-1, 3)
+        total = torch.zeros((count, 3), dtype=torch.float64, device=coord.device).index_add_(0, inverse, kept.double())
+        members = torch.bincount(inverse, minlength=count).double()
+        mean = (total / members[:, None]).to(coord.dtype)
+        lo = torch.full((count, 3), float("inf"), dtype=coord.dtype, device=coord.device).scatter_reduce_(0, rows, kept, "amin")
+        hi = torch.full((count, 3), float("-inf"), dtype=coord.dtype, device=coord.device).scatter_reduce_(0, rows, kept, "amax")
+        center = torch.full((coord.shape[0], 3), float(self.instance_ignore_index), dtype=coord.dtype, device=coord.device)
+        center[mask] = mean[inverse]
+        data_dict["instance"] = instance
+        data_dict["instance_center"] = center
+        data_dict["bbox"] = torch.cat([lo, hi], 1)
         return data_dict
 
 
