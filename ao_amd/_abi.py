@@ -149,3 +149,10 @@ if not os.path.exists(PG_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % PG_HEADER)
 with open(PG_HEADER) as _f:
     pg_consts, pg_structs, pg_signatures = parse(_f.read())
+
+# the eighth public header (Masked Scene Contrast: InfoNCE over matched pairs, pair matching, patch ids), likewise
+MSC_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_msc_hip.h")
+if not os.path.exists(MSC_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % MSC_HEADER)
+with open(MSC_HEADER) as _f:
+    msc_consts, msc_structs, msc_signatures = parse(_f.read())

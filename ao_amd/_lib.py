@@ -38,6 +38,8 @@ EXPECTED_PTV1_ABI = 1
 EXPECTED_SPCONV_ABI = 1
 # the same for include/ptv2_pg_hip.h and ptv2_pg_abi_version() (ao_amd/csrc/pointgroup.hip)
 EXPECTED_PG_ABI = 1
+# the same for include/ptv2_msc_hip.h and ptv2_msc_abi_version() (ao_amd/csrc/msc.hip)
+EXPECTED_MSC_ABI = 1
 
 
 def build(verbose=False):
@@ -56,7 +58,7 @@ def lib():
                 "or `make -C ao_amd/csrc` (needs hipcc). There is no CPU fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures, _abi.pp2s_signatures,
-                      _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures):
+                      _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures, _abi.msc_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -99,6 +101,10 @@ def lib():
         if handle.ptv2_pg_struct_bytes(0) != ctypes.sizeof(_abi.pg_structs["pg_csr"]):
             raise RuntimeError("ao_amd: pg_csr is %d bytes in python, %d in %s (stale build)" % (
                 ctypes.sizeof(_abi.pg_structs["pg_csr"]), handle.ptv2_pg_struct_bytes(0), LIB_PATH))
+        have = handle.ptv2_msc_abi_version()
+        if have != EXPECTED_MSC_ABI:
+            raise RuntimeError("ao_amd: %s has msc ABI version %d, the python side expects %d -- stale build; rebuild with "
+                               "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_MSC_ABI))
         for which, name in enumerate(("ptv1_params", "ptv1_norms", "ptv1_grads")):
             if handle.ptv2_ptv1_struct_bytes(which) != ctypes.sizeof(_abi.ptv1_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

@@ -33,9 +33,15 @@ per-point transforms.  Every host-side random decision (gate, angle, scale, blen
 torch.Generator or is passed by keyword; per-point normals come from a 64-bit `seed` (in-kernel Philox4x32-10, counter =
 point index and the step's stream number) or from a `noise=` tensor.
 
-Not here, on purpose: RandomDropout, HueSaturationTranslation, RandomColorJitter / RandomColorGrayScale (commented out in
-every PT-v2m2 config, or active only in one ScanNet list with a ratio the data-efficient benchmarks use), NormalizeCoord,
-PositiveShift, CropBoundary and the contrastive transforms (ContrastiveViewsGenerator), which belong to other model families.
+Not here, on purpose: RandomDropout, HueSaturationTranslation, RandomColorGrayScale (commented out in every PT-v2m2 config, or
+active only in one ScanNet list with a ratio the data-efficient benchmarks use), NormalizeCoord, PositiveShift and CropBoundary,
+which belong to other model families.
+
+ContrastiveViewsGenerator (:1046-1067) and RandomColorJitter (:440-630) are here for Masked Scene Contrast (ao_amd/msc): with
+them `Compose(cfg)` builds the whole transform list of both MSC-v1m1 ScanNet configs.  RandomColorJitter is plain torch on the
+device, one tensor operation per numpy operation of the reference and in the dtype numpy gives that operation (the hue path is
+float64 from the saturation on, as `maxc * (1 - eqc)` multiplies a float32 array by an int64 one): brightness, saturation and
+hue equal the numpy results bit for bit, contrast to the order of its one mean.
 
 InstanceParser (:1071-1104) is here for PointGroup (ao_amd/pointgroup): torch segment reductions on whatever device the data
 is on instead of the reference's loop over the instances.
@@ -44,6 +50,7 @@ import copy
 import ctypes
 import inspect
 import math
+import numbers
 
 import torch
 
@@ -451,8 +458,14 @@ class Compose:
 
     def __init__(self, cfg=None, fuse=False, generator=None, device_generator=None):
         self.cfg = cfg if cfg is not None else []
-        self.transforms = [t if callable(t) else build_transform(t) for t in self.cfg]
         self.fuse, self.generator, self.device_generator = fuse, generator, device_generator
+        self.transforms = [t if callable(t) else build_transform(self._views_cfg(t)) for t in self.cfg]
+
+    def _views_cfg(self, cfg):
+        """a ContrastiveViewsGenerator named by a config entry runs its inner list as this Compose runs its own"""
+        if cfg.get("type") != "ContrastiveViewsGenerator":
+            return cfg
+        return dict(dict(fuse=self.fuse, generator=self.generator, device_generator=self.device_generator), **cfg)
 
     def groups(self):
         """[(is a per-point run, [indices into self.transforms])]"""
@@ -493,7 +506,7 @@ class Compose:
                 data_dict = _run_records(self.records(idx, draws), data_dict, draws["seed"], final_round=True)
                 continue
             t = self.transforms[idx[0]]
-            g = self.generator if isinstance(t, ShufflePoint) else self.device_generator
+            g = self.generator if isinstance(t, (ShufflePoint, RandomColorJitter)) else self.device_generator
             takes = g is not None and "generator" in inspect.signature(t.__call__).parameters
             data_dict = t(data_dict, generator=g) if takes else t(data_dict)
         return data_dict
@@ -855,13 +868,175 @@ class RandomColorDrop(_PointTransform):
         return [dict(kind=_K["PTV2_AUG_COLOR_MUL"], p=[float(self.color_augment)])] if draws["gate"] < self.p else []
 
 
+class RandomColorJitter:
+    """transform.py:440-630 on a float32 `color` in [0, 255].  The host-side decisions come from `generator` in the reference's
+    get_params order -- the order of the four adjustments (torch.randperm(4)), then the brightness, contrast, saturation and hue
+    factor of those that are switched on -- followed by one gate per adjustment that is reached, in application order; or
+    from `draws` = dict(order=(4 ints), factors=(b, c, s, h; None where switched off), gates=(4 floats, by position in order))."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, p=0.95):
+        self.brightness = self._check_input(brightness, "brightness")
+        self.contrast = self._check_input(contrast, "contrast")
+        self.saturation = self._check_input(saturation, "saturation")
+        self.hue = self._check_input(hue, "hue", center=0, bound=(-0.5, 0.5), clip_first_on_zero=False)
+        self.p = p
+
+    @staticmethod
+    def _check_input(value, name, center=1, bound=(0, float("inf")), clip_first_on_zero=True):
+        if isinstance(value, numbers.Number):
+            if value < 0:
+                raise ValueError("If {} is a single number, it must be non negative.".format(name))
+            value = [center - float(value), center + float(value)]
+            if clip_first_on_zero:
+                value[0] = max(value[0], 0.0)
+        elif isinstance(value, (tuple, list)) and len(value) == 2:
+            if not bound[0] <= value[0] <= value[1] <= bound[1]:
+                raise ValueError("{} values should be between {}".format(name, bound))
+        else:
+            raise TypeError("{} should be a single number or a list/tuple with length 2.".format(name))
+        # if value is 0 or (1., 1.) for brightness/contrast/saturation or (0., 0.) for hue, do nothing
+        if value[0] == value[1] == center:
+            value = None
+        return value
+
+    @staticmethod
+    def _scalar(value, like):
+        """a python float against an array of `like`'s dtype: numpy rounds it to that dtype first.  (A tensor, not a python
+        scalar: torch divides by a python scalar through its rounded reciprocal on the GPU.)"""
+        return torch.full((1,), float(value), dtype=like.dtype, device=like.device)
+
+    @classmethod
+    def blend(cls, color1, color2, ratio):
+        ratio = float(ratio)
+        first = cls._scalar(ratio, color1) * color1
+        second = cls._scalar(1.0 - ratio, color1) * color2
+        return (first + second).clamp(0, 255.0).to(color1.dtype)
+
+    @classmethod
+    def rgb_to_grayscale(cls, color):
+        r, g, b = color[..., 0], color[..., 1], color[..., 2]
+        gray = cls._scalar(0.2989, color) * r + cls._scalar(0.587, color) * g
+        gray = gray + cls._scalar(0.114, color) * b
+        return gray.unsqueeze(-1)
+
+    @classmethod
+    def rgb2hsv(cls, rgb):
+        r, g, b = rgb[..., 0], rgb[..., 1], rgb[..., 2]
+        maxc = rgb.max(dim=-1)[0]
+        minc = rgb.min(dim=-1)[0]
+        eqc = maxc == minc
+        cr = maxc - minc
+        ones = (torch.ones_like(maxc) * eqc).double()
+        neq = (1 - eqc.long()).double()  # (int64 in numpy; float32 * int64 is float64 there: everything from here on)
+        wide = maxc.double()
+        s = cr.double() / (ones + wide * neq)
+        cr_divisor = ones + cr.double() * neq
+        rc = (maxc - r).double() / cr_divisor
+        gc = (maxc - g).double() / cr_divisor
+        bc = (maxc - b).double() / cr_divisor
+        hr = (maxc == r).double() * (bc - gc)
+        hg = ((maxc == g) & (maxc != r)).double() * (2.0 + rc - bc)
+        hb = ((maxc != g) & (maxc != r)).double() * (4.0 + gc - rc)
+        h = hr + hg + hb
+        h = torch.remainder(h / cls._scalar(6.0, h) + 1.0, 1.0)
+        return torch.stack((h, s, wide), dim=-1)
+
+    @staticmethod
+    def hsv2rgb(hsv):
+        h, s, v = hsv[..., 0], hsv[..., 1], hsv[..., 2]
+        i = torch.floor(h * 6.0)
+        f = (h * 6.0) - i
+        i = i.to(torch.int32)
+        p = (v * (1.0 - s)).clamp(0.0, 1.0)
+        q = (v * (1.0 - s * f)).clamp(0.0, 1.0)
+        t = (v * (1.0 - s * (1.0 - f))).clamp(0.0, 1.0)
+        i = torch.remainder(i, 6).long().unsqueeze(-1)
+        # (the reference's einsum with a one-hot mask adds five zeros to the selected entry)
+        a1 = torch.stack((v, q, p, p, t, v), dim=-1).gather(-1, i)
+        a2 = torch.stack((t, v, v, q, p, p), dim=-1).gather(-1, i)
+        a3 = torch.stack((p, p, t, v, v, q), dim=-1).gather(-1, i)
+        return torch.cat((a1, a2, a3), dim=-1)
+
+    def adjust_brightness(self, color, brightness_factor):
+        if brightness_factor < 0:
+            raise ValueError("brightness_factor ({}) is not non-negative.".format(brightness_factor))
+        return self.blend(color, torch.zeros_like(color), brightness_factor)
+
+    def adjust_contrast(self, color, contrast_factor):
+        if contrast_factor < 0:
+            raise ValueError("contrast_factor ({}) is not non-negative.".format(contrast_factor))
+        mean = self.rgb_to_grayscale(color).mean()
+        return self.blend(color, mean, contrast_factor)
+
+    def adjust_saturation(self, color, saturation_factor):
+        if saturation_factor < 0:
+            raise ValueError("saturation_factor ({}) is not non-negative.".format(saturation_factor))
+        return self.blend(color, self.rgb_to_grayscale(color), saturation_factor)
+
+    def adjust_hue(self, color, hue_factor):
+        if not (-0.5 <= hue_factor <= 0.5):
+            raise ValueError("hue_factor ({}) is not in [-0.5, 0.5].".format(hue_factor))
+        hsv = self.rgb2hsv(color / self._scalar(255.0, color))
+        h, s, v = hsv[..., 0], hsv[..., 1], hsv[..., 2]
+        h = torch.remainder(h + float(hue_factor), 1.0)
+        hsv = torch.stack((h, s, v), dim=-1)
+        return (self.hsv2rgb(hsv) * 255.0).to(color.dtype)
+
+    def get_params(self, generator=None):
+        order = torch.randperm(4, generator=generator).tolist()
+        factors = [None if r is None else float(_uniform(r[0], r[1], (), generator))
+                   for r in (self.brightness, self.contrast, self.saturation, self.hue)]
+        return order, factors
+
+    def __call__(self, data_dict, generator=None, draws=None):
+        if draws is None:
+            order, factors = self.get_params(generator)
+            gates = None
+        else:
+            order, factors, gates = [int(v) for v in draws["order"]], list(draws["factors"]), list(draws["gates"])
+        adjust = (self.adjust_brightness, self.adjust_contrast, self.adjust_saturation, self.adjust_hue)
+        for at, fn_id in enumerate(order):
+            if factors[fn_id] is None:
+                continue
+            gate = float(torch.rand((), dtype=torch.float64, generator=generator)) if gates is None else float(gates[at])
+            if gate < self.p:
+                data_dict["color"] = adjust[fn_id](data_dict["color"], factors[fn_id])
+        return data_dict
+
+
+class ContrastiveViewsGenerator:
+    """transform.py:1046-1067: the `view_keys` cloned twice, `view_trans_cfg` run over either copy, the results written back as
+    `view1_*` and `view2_*`.  fuse, generator and device_generator go to the inner Compose; the two views take successive
+    draws from the same generators."""
+
+    def __init__(self, view_keys=("coord", "color", "normal", "origin_coord"), view_trans_cfg=None, fuse=False, generator=None,
+                 device_generator=None):
+        self.view_keys = view_keys
+        self.view_trans = Compose(view_trans_cfg, fuse=fuse, generator=generator, device_generator=device_generator)
+
+    def __call__(self, data_dict):
+        view1_dict = dict()
+        view2_dict = dict()
+        for key in self.view_keys:
+            view1_dict[key] = data_dict[key].clone()
+            view2_dict[key] = data_dict[key].clone()
+        view1_dict = self.view_trans(view1_dict)
+        view2_dict = self.view_trans(view2_dict)
+        for key, value in view1_dict.items():
+            data_dict["view1_" + key] = value
+        for key, value in view2_dict.items():
+            data_dict["view2_" + key] = value
+        return data_dict
+
+
 _TRANSFORMS = dict(GridSample=GridSample, SphereCrop=SphereCrop, Collect=Collect, CenterShift=CenterShift,
                    NormalizeColor=NormalizeColor, RandomScale=RandomScale, RandomFlip=RandomFlip,
                    RandomRotateTargetAngle=RandomRotateTargetAngle, ToTensor=ToTensor, Copy=Copy, RandomRotate=RandomRotate,
                    RandomShift=RandomShift, RandomJitter=RandomJitter, ElasticDistortion=ElasticDistortion,
                    ChromaticAutoContrast=ChromaticAutoContrast, ChromaticTranslation=ChromaticTranslation,
                    ChromaticJitter=ChromaticJitter, RandomColorDrop=RandomColorDrop, PointClip=PointClip,
-                   ShufflePoint=ShufflePoint)
+                   ShufflePoint=ShufflePoint, RandomColorJitter=RandomColorJitter,
+                   ContrastiveViewsGenerator=ContrastiveViewsGenerator)
 
 
 def point_collate(batch, mix_prob=0, generator=None, mix=None):
@@ -877,6 +1052,8 @@ def point_collate(batch, mix_prob=0, generator=None, mix=None):
         else:
             out[key] = list(vals)
     dev = out["coord"].device if "coord" in out else None
+    if dev is None:  # (the contrastive lists collect view1_coord / view2_coord: the device of the first tensor that is on one)
+        dev = next((v.device for v in out.values() if torch.is_tensor(v) and v.is_cuda), None)
     host = {}
     for key in out:
         if "offset" in key and torch.is_tensor(out[key]):
