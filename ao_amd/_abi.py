@@ -156,3 +156,11 @@ if not os.path.exists(MSC_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % MSC_HEADER)
 with open(MSC_HEADER) as _f:
     msc_consts, msc_structs, msc_signatures = parse(_f.read())
+
+# the ninth public header (Stratified Transformer: window cells, pair lists, the pointops2 attention operators, fused window
+# attention), likewise
+ST_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_st_hip.h")
+if not os.path.exists(ST_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % ST_HEADER)
+with open(ST_HEADER) as _f:
+    st_consts, st_structs, st_signatures = parse(_f.read())

@@ -40,6 +40,8 @@ EXPECTED_SPCONV_ABI = 1
 EXPECTED_PG_ABI = 1
 # the same for include/ptv2_msc_hip.h and ptv2_msc_abi_version() (ao_amd/csrc/msc.hip)
 EXPECTED_MSC_ABI = 1
+# the same for include/ptv2_st_hip.h and ptv2_st_abi_version() (ao_amd/csrc/stratified.hip)
+EXPECTED_ST_ABI = 1
 
 
 def build(verbose=False):
@@ -58,7 +60,8 @@ def lib():
                 "or `make -C ao_amd/csrc` (needs hipcc). There is no CPU fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures, _abi.pp2s_signatures,
-                      _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures, _abi.msc_signatures):
+                      _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures, _abi.msc_signatures,
+                      _abi.st_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -105,6 +108,13 @@ def lib():
         if have != EXPECTED_MSC_ABI:
             raise RuntimeError("ao_amd: %s has msc ABI version %d, the python side expects %d -- stale build; rebuild with "
                                "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_MSC_ABI))
+        have = handle.ptv2_st_abi_version()
+        if have != EXPECTED_ST_ABI:
+            raise RuntimeError("ao_amd: %s has st ABI version %d, the python side expects %d -- stale build; rebuild with "
+                               "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_ST_ABI))
+        if handle.ptv2_st_struct_bytes(0) != ctypes.sizeof(_abi.st_structs["st_args"]):
+            raise RuntimeError("ao_amd: st_args is %d bytes in python, %d in %s (stale build)" % (
+                ctypes.sizeof(_abi.st_structs["st_args"]), handle.ptv2_st_struct_bytes(0), LIB_PATH))
         for which, name in enumerate(("ptv1_params", "ptv1_norms", "ptv1_grads")):
             if handle.ptv2_ptv1_struct_bytes(which) != ctypes.sizeof(_abi.ptv1_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

@@ -7,6 +7,8 @@ from ..pointops.interpolation import interpolation_index_weight, _InterpolateRow
 from ..pointops.query import knn_query_dist2
 from ..pointops.sampling import farthest_point_sampling as furthestsampling  # noqa: F401
 from ..pointops.subtraction import subtraction  # noqa: F401
+from ..stratified.ops import (attention_step1_v2, attention_step2_with_rel_pos_value_v2,  # noqa: F401  (:169-257, :853-960,
+                              dot_prod_with_idx_v3)                                        # :631-754)
 
 
 def knnquery(nsample, xyz, new_xyz, offset, new_offset):
@@ -40,3 +42,20 @@ def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
 
 
 interpolation2 = interpolation
+
+
+def _not_provided(name):
+    def op(*args, **kwargs):
+        raise NotImplementedError("pointops2.%s is not provided: ST-v1m2 with rel_query = rel_key = rel_value = True calls "
+                                  "attention_step1_v2, dot_prod_with_idx_v3 and attention_step2_with_rel_pos_value_v2 only" % name)
+    op.__name__ = name
+    return op
+
+
+# the older forms of the three operators above; no ST-v1m2 code path with the configs' flags reaches them
+attention_step1 = _not_provided("attention_step1")
+attention_step2 = _not_provided("attention_step2")
+attention_step2_v2 = _not_provided("attention_step2_v2")
+dot_prod_with_idx = _not_provided("dot_prod_with_idx")
+dot_prod_with_idx_v2 = _not_provided("dot_prod_with_idx_v2")
+attention_step2_with_rel_pos_value = _not_provided("attention_step2_with_rel_pos_value")

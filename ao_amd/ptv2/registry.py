@@ -33,8 +33,8 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
     segmentor and `Criteria` then builds it from the same config entry; with TEST (pointcept/engines/test.py:26) the whole-scene
     tester of ao_amd/ptv2/tester.py under "SemSegTester", which `test = dict(type="SemSegTester")` then resolves to.  Every
     registry may be omitted.  MODELS also receives
-    CACSegmentor under "CAC-v1m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", PointGroup under "PG-v1m1" and MaskedSceneContrast
-    under "MSC-v1m1"; the returned
+    CACSegmentor under "CAC-v1m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", PointGroup under "PG-v1m1", MaskedSceneContrast
+    under "MSC-v1m1" and StratifiedTransformer under "ST-v1m2" and "STv1m2"; the returned
     list of names leaves those entries out (it predates them)."""
     done = []
     if MODELS is not None:
@@ -66,6 +66,11 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
         from ..msc import MaskedSceneContrast
 
         _register(MODELS, MaskedSceneContrast, "MSC-v1m1", force)
+        # Stratified Transformer (ao_amd/stratified) under both spellings the reference's configs use, likewise
+        from ..stratified import StratifiedTransformer
+
+        _register(MODELS, StratifiedTransformer, "ST-v1m2", force)
+        _register(MODELS, StratifiedTransformer, "STv1m2", force)
     if OPTIMIZERS is not None:
         from .optim import FlatAdamW
 
