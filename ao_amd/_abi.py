@@ -164,3 +164,10 @@ if not os.path.exists(ST_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % ST_HEADER)
 with open(ST_HEADER) as _f:
     st_consts, st_structs, st_signatures = parse(_f.read())
+
+# the tenth public header (the instance-segmentation evaluator's association pass), likewise
+INSEVAL_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_inseval_hip.h")
+if not os.path.exists(INSEVAL_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % INSEVAL_HEADER)
+with open(INSEVAL_HEADER) as _f:
+    inseval_consts, inseval_structs, inseval_signatures = parse(_f.read())

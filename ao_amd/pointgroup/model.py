@@ -68,9 +68,10 @@ class PointGroup(nn.Module):
         return dict(loss=loss, seg_loss=seg_loss, bias_l1_loss=bias_l1_loss, bias_cosine_loss=bias_cosine_loss)
 
     @torch.no_grad()
-    def propose(self, coord, offset, bias_pred, logit_pred):
-        """(pred_scores (P) fp32, pred_masks (P, N) int32, pred_classes (P) int64) as CPU tensors: the clusters of the shifted
-        points (coord + bias_pred) / voxel_size within cluster_thresh among the points whose predicted class is not ignored."""
+    def propose_device(self, coord, offset, bias_pred, logit_pred):
+        """(pred_scores (P) fp32, pred_masks (P, N) int32, pred_classes (P) int64) on the device: the clusters of the shifted
+        points (coord + bias_pred) / voxel_size within cluster_thresh among the points whose predicted class is not ignored.
+        What ao_amd/pointgroup/evaluate.py reads in place: the masks never leave the device."""
         _lib.require_cuda(coord, offset, bias_pred, logit_pred)
         n = coord.shape[0]
         center_pred = ((coord.float() + bias_pred.float()) / self.voxel_size)
@@ -81,7 +82,9 @@ class PointGroup(nn.Module):
             mask &= segment_pred != index
         kept = mask.nonzero().view(-1)
         if kept.numel() == 0:  # (the reference raises here)
-            return torch.zeros(0), torch.zeros((0, n), dtype=torch.int32), torch.zeros(0, dtype=torch.int64)
+            dev = coord.device
+            return (torch.zeros(0, device=dev), torch.zeros((0, n), dtype=torch.int32, device=dev),
+                    torch.zeros(0, dtype=torch.int64, device=dev))
         offset = offset.long()
         batch = torch.searchsorted(offset, kept, right=True)  # offset2batch(offset)[mask]
         counts = torch.bincount(batch, minlength=offset.numel())
@@ -93,6 +96,12 @@ class PointGroup(nn.Module):
         point_cluster[kept] = sub_cluster
         scores, masks, classes = ops.proposals(point_cluster, sizes, kept[firsts.long()].int(), segment_pred, prob,
                                                self.cluster_propose_points)
+        return scores, masks, classes
+
+    @torch.no_grad()
+    def propose(self, coord, offset, bias_pred, logit_pred):
+        """propose_device(...) as CPU tensors: what the reference's forward returns"""
+        scores, masks, classes = self.propose_device(coord, offset, bias_pred, logit_pred)
         return scores.cpu(), masks.cpu(), classes.cpu()
 
     def forward(self, data_dict):

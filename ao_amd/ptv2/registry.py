@@ -27,7 +27,7 @@ def _register(registry, cls, name, force):
         registry.register_module(module=cls, name=name)
 
 
-def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
+def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, HOOKS=None):
     """Put PT-v2m2, the three segmentors (CAC-v1m1 included) and FlatAdamW under the reference's registry names, and with LOSSES
     (pointcept/models/losses/builder.py) the HIP LovaszLoss under "LovaszLoss": a trainer that keeps the reference's own
     segmentor and `Criteria` then builds it from the same config entry; with TEST (pointcept/engines/test.py:26) the whole-scene
@@ -35,7 +35,8 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
     registry may be omitted.  MODELS also receives
     CACSegmentor under "CAC-v1m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", PointGroup under "PG-v1m1", MaskedSceneContrast
     under "MSC-v1m1" and StratifiedTransformer under "ST-v1m2" and "STv1m2"; the returned
-    list of names leaves those entries out (it predates them)."""
+    list of names leaves those entries out (it predates them).  With HOOKS (pointcept/engines/hooks/builder.py) the instance
+    evaluator of ao_amd/pointgroup/evaluate.py is filed under "InsSegEvaluator", likewise not listed."""
     done = []
     if MODELS is not None:
         from .model import PointTransformerV2
@@ -86,4 +87,8 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None):
 
         _register(TEST, SemSegTester, "SemSegTester", force)
         done.append("SemSegTester")
+    if HOOKS is not None:
+        from ..pointgroup.evaluate import InsSegEvaluator
+
+        _register(HOOKS, InsSegEvaluator, "InsSegEvaluator", force)
     return done
