@@ -171,3 +171,10 @@ if not os.path.exists(INSEVAL_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % INSEVAL_HEADER)
 with open(INSEVAL_HEADER) as _f:
     inseval_consts, inseval_structs, inseval_signatures = parse(_f.read())
+
+# the eleventh public header (Masked Scene Contrast v1m2: the partitioned InfoNCE loss of CSC), likewise
+CSC_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_csc_hip.h")
+if not os.path.exists(CSC_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % CSC_HEADER)
+with open(CSC_HEADER) as _f:
+    csc_consts, csc_structs, csc_signatures = parse(_f.read())

@@ -1,6 +1,8 @@
 """Masked Scene Contrast (MSC-v1m1, pointcept/models/masked_scene_contrast/masked_scene_contrast_v1m1_base.py) on the MI355X:
 the reference's constructor keywords and defaults, state-dict keys (`backbone.*`, `mask_token`, `color_head.*`, `normal_head.*`)
-and returned dict, over ao_amd/msc/ops.py.
+and returned dict, over ao_amd/msc/ops.py.  MaskedSceneContrastCSC is MSC-v1m2 (masked_scene_contrast_v1m2_csc.py): the same
+forward with the partitioned InfoNCE loss of ops.csc_nce, which reads the unaugmented coordinates and the unmixed offsets
+(DESIGN.md section 16).
 
 What differs from the reference: the (M, M) similarity matrix and the padded patch-to-point map are never
 formed; no matched pair raises ValueError where the reference returns a NaN loss; nothing is read back in the loss; with more than one rank the returned nce_loss
@@ -62,7 +64,10 @@ class MaskedSceneContrast(nn.Module):
 
     def compute_contrastive_loss(self, view1_feat, view1_offset, view2_feat, view2_offset, match_index):
         assert view1_offset.shape == view2_offset.shape
-        loss, pos_sim, neg_sim = ops.info_nce(view1_feat, view2_feat, match_index, self.nce_t)
+        return self._over_ranks(*ops.info_nce(view1_feat, view2_feat, match_index, self.nce_t))
+
+    @staticmethod
+    def _over_ranks(loss, pos_sim, neg_sim):
         world = _world_size()
         if world > 1:
             # :195-203.  The reference all-reduces the loss itself, which cuts its graph; here the sum over the ranks is taken
@@ -75,6 +80,10 @@ class MaskedSceneContrast(nn.Module):
             dist.all_reduce(pos_sim)
             dist.all_reduce(neg_sim)
         return loss / world, pos_sim / world, neg_sim / world
+
+    def _contrastive_loss(self, view1_feat, view1_origin_coord, view1_offset, view2_feat, view2_origin_coord, view2_offset,
+                          match_index):
+        return self.compute_contrastive_loss(view1_feat, view1_offset, view2_feat, view2_offset, match_index)
 
     def _backbone(self, data, which, mixed):
         try:
@@ -137,7 +146,8 @@ class MaskedSceneContrast(nn.Module):
             view1_origin_coord, view1_offset, view2_origin_coord, view2_offset, max_k=self.matching_max_k,
             max_radius=self.matching_max_radius, row_draws=draws.get("row_draws"), perm=draws.get("pair_perm"),
             generator=draws.get("generator"))
-        nce_loss, pos_sim, neg_sim = self.compute_contrastive_loss(view1_feat, view1_offset, view2_feat, view2_offset, match_index)
+        nce_loss, pos_sim, neg_sim = self._contrastive_loss(view1_feat, view1_origin_coord, view1_offset, view2_feat,
+                                                            view2_origin_coord, view2_offset, match_index)
         loss = nce_loss * self.contrast_weight
         result_dict = dict(nce_loss=nce_loss, pos_sim=pos_sim, neg_sim=neg_sim)
 
@@ -175,3 +185,35 @@ class MaskedSceneContrast(nn.Module):
 
         result_dict["loss"] = loss
         return result_dict
+
+
+class MaskedSceneContrastCSC(MaskedSceneContrast):
+    """MSC-v1m2: the reference's keywords and defaults (r2 = 2 there; its ScanNet config sets r1 = 2, r2 = 20, mask_rate = 0 and
+    no heads), the state-dict keys of MSC-v1m1, and the same returned dict."""
+
+    def __init__(self, backbone, backbone_in_channels, backbone_out_channels, mask_grid_size=0.1, mask_rate=0.4, view1_mix_prob=0,
+                 view2_mix_prob=0, matching_max_k=8, matching_max_radius=0.03, matching_max_pair=8192, nce_t=0.4,
+                 contrast_weight=1, reconstruct_weight=1, reconstruct_color=True, reconstruct_normal=True, partitions=4, r1=0.125,
+                 r2=2):
+        super().__init__(backbone, backbone_in_channels, backbone_out_channels, mask_grid_size=mask_grid_size, mask_rate=mask_rate,
+                         view1_mix_prob=view1_mix_prob, view2_mix_prob=view2_mix_prob, matching_max_k=matching_max_k,
+                         matching_max_radius=matching_max_radius, matching_max_pair=matching_max_pair, nce_t=nce_t,
+                         contrast_weight=contrast_weight, reconstruct_weight=reconstruct_weight,
+                         reconstruct_color=reconstruct_color, reconstruct_normal=reconstruct_normal)
+        self.partitions = partitions
+        self.r1 = r1
+        self.r2 = r2
+
+    def compute_partitions(self, coord1, coord2):
+        """:182-200, the eager statements: (len(coord2), len(coord1)) fp32 with -1e7, 0, 1, 2, 3.  The loss does not form it."""
+        return ops.compute_partitions_torch(coord1, coord2, self.r1, self.r2)
+
+    def compute_contrastive_loss(self, view1_feat, view1_coord, view1_offset, view2_feat, view2_coord, view2_offset, match_index):
+        assert view1_offset.shape == view2_offset.shape
+        return self._over_ranks(*ops.csc_nce(view1_feat, view2_feat, view1_coord, view2_coord, view1_offset, match_index,
+                                             self.nce_t, self.r1, self.r2, self.partitions))
+
+    def _contrastive_loss(self, view1_feat, view1_origin_coord, view1_offset, view2_feat, view2_origin_coord, view2_offset,
+                          match_index):
+        return self.compute_contrastive_loss(view1_feat, view1_origin_coord, view1_offset, view2_feat, view2_origin_coord,
+                                             view2_offset, match_index)

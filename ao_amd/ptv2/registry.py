@@ -34,7 +34,7 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, H
     tester of ao_amd/ptv2/tester.py under "SemSegTester", which `test = dict(type="SemSegTester")` then resolves to.  Every
     registry may be omitted.  MODELS also receives
     CACSegmentor under "CAC-v1m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", PointGroup under "PG-v1m1", MaskedSceneContrast
-    under "MSC-v1m1" and StratifiedTransformer under "ST-v1m2" and "STv1m2"; the returned
+    under "MSC-v1m1", MaskedSceneContrastCSC under "MSC-v1m2" and StratifiedTransformer under "ST-v1m2" and "STv1m2"; the returned
     list of names leaves those entries out (it predates them).  With HOOKS (pointcept/engines/hooks/builder.py) the instance
     evaluator of ao_amd/pointgroup/evaluate.py is filed under "InsSegEvaluator", likewise not listed."""
     done = []
@@ -64,9 +64,10 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, H
 
         _register(MODELS, PointGroup, "PG-v1m1", force)
         # Masked Scene Contrast (ao_amd/msc), likewise filed and not listed
-        from ..msc import MaskedSceneContrast
+        from ..msc import MaskedSceneContrast, MaskedSceneContrastCSC
 
         _register(MODELS, MaskedSceneContrast, "MSC-v1m1", force)
+        _register(MODELS, MaskedSceneContrastCSC, "MSC-v1m2", force)
         # Stratified Transformer (ao_amd/stratified) under both spellings the reference's configs use, likewise
         from ..stratified import StratifiedTransformer
 

@@ -43,6 +43,9 @@ device, one tensor operation per numpy operation of the reference and in the dty
 float64 from the saturation on, as `maxc * (1 - eqc)` multiplies a float32 array by an int64 one): brightness, saturation and
 hue equal the numpy results bit for bit, contrast to the order of its one mean.
 
+`pair_views` is ScanNetPairDataset.prepare_train_data (datasets/scannet_pair.py:70-80) for the MSC-v1m2 (CSC) config, whose two
+views come from two frames of a scene and go through a transform list each.
+
 InstanceParser (:1071-1104) is here for PointGroup (ao_amd/pointgroup): torch segment reductions on whatever device the data
 is on instead of the reference's loop over the instances.
 """
@@ -1027,6 +1030,19 @@ class ContrastiveViewsGenerator:
         for key, value in view2_dict.items():
             data_dict["view2_" + key] = value
         return data_dict
+
+
+def pair_views(view1_dict, view2_dict, view1_transform, view2_transform):
+    """datasets/scannet_pair.py:70-80: either view through its own transform (a Compose, or any callable on a dict), the results
+    under `view1_*` and `view2_*` in one dict -- what point_collate and MaskedSceneContrastCSC then take."""
+    view1_dict = view1_transform(view1_dict)
+    view2_dict = view2_transform(view2_dict)
+    data_dict = dict()
+    for key, value in view1_dict.items():
+        data_dict["view1_" + key] = value
+    for key, value in view2_dict.items():
+        data_dict["view2_" + key] = value
+    return data_dict
 
 
 _TRANSFORMS = dict(GridSample=GridSample, SphereCrop=SphereCrop, Collect=Collect, CenterShift=CenterShift,
