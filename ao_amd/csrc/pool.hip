@@ -189,7 +189,7 @@ extern "C" int segment_sum_hip_launcher(int n_out, int c, const float *grad_fine
                                         float *grad_coarse, void *stream) {
     if (n_out < 0 || c < 1 || !grad_fine || !order || !idx_ptr || !grad_coarse) return PTV2_ERR_ARG;
     if (n_out == 0) return PTV2_OK;
-    const bool vec = c % 4 == 0;
+    const bool vec = c % 4 == 0 && (((uintptr_t)grad_fine | (uintptr_t)grad_coarse) & 15) == 0;   // float4 rows: 16-byte bases
     const int cv = vec ? c / 4 : c;
     const long long total = (long long)n_out * cv;
     const int nblk = (int)std::min<long long>((total + TPB - 1) / TPB, 256 * 16);

@@ -392,6 +392,9 @@ int ptv2_gva_plan_describe(int n, int k, int c, int g, int attn_drop, int has_in
  *   segment_minmax: per-cloud coordinate min/max, lo/hi (b,3)                         (:249-253)
  *   pool_max:       out[j,:] = max over rows order[idx_ptr[j]..idx_ptr[j+1]) of feat; arg = winning row
  *                   (first wins ties); backward scatters grad_out to grad_feat[arg] [zeroed]   (:266)
+ *                   Every cluster has at least one member (idx_ptr strictly ascending), as grid_pool builds them: an
+ *                   empty cluster is NOT part of pool_max's contract (the kernel reads the first member before it looks
+ *                   at the length).  segment_sum takes an empty cluster and writes zeros.
  */
 /*   grid_pool:     the whole coordinate half of GridPool.forward (:246-268): voxel ids (grid_cluster formula,
  *                  batch-major), stable sort, cluster ranks, pooled coordinates (mean in ascending point order),
