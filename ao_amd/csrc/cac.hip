@@ -631,7 +631,8 @@ extern "C" int cac_distill_forward_hip_launcher(int n, int k, const float *pred,
     if (n < 1 || k < 1 || k > MAXK || !pred || !soft || !label || !loss || !coef) return PTV2_ERR_ARG;
     const int chunks = divup(n, CHUNK);
     const size_t part_bytes = sizeof(float) * (size_t)chunks * 3 * k;
-    if (!workspace || workspace_bytes < part_bytes + ptv2_align256(sizeof(float) * 3 * k)) return PTV2_ERR_WORKSPACE;
+    // the layout below: part at 0, sums (3 k floats) at the next 256-byte boundary
+    if (!workspace || workspace_bytes < ptv2_align256(part_bytes) + sizeof(float) * 3 * k) return PTV2_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace, *sums = (float *)((char *)workspace + ptv2_align256(part_bytes));
     hipLaunchKernelGGL(distill_partial_kernel, dim3(chunks), dim3(TPB), 0, st, n, k, pred, soft, label, part);
