@@ -41,6 +41,7 @@ struct PtvCarver {
 //   AO_AMD_TILE_KEEP_A        gva_plan.hip: gva_plan()   per call   set: the tile forward writes A (the A-reading weight gradient)
 //   AO_AMD_LOGITS_BWD         gva_plan.hip: gva_plan()   per call   "staged": the three-kernel logits backward (first letter s)
 //   AO_AMD_BN_FINAPPLY        bn.hip                     per call   0: separate finalize + apply launches (bn_finapply_off())
+//   AO_AMD_SKINNY             skinny.hip                 per call   "lanes": the lane forms of the G-wide projection and of its backward + reduce (first letter l)
 //   AO_AMD_GEMM               gemm.hip                   per call   "direct" | "lds": the older row GEMM forms (plain getenv: first letter d / l)
 //   AO_AMD_FPS_LOCAL          fps.hip                    per call   0: the device-scope exchange instead of one XCD per cloud
 //   AO_AMD_GRAPH_IDLE_EAGER   graph.hip                  per call   0: launch the graph also when the stream is idle
