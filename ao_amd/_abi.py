@@ -178,3 +178,10 @@ if not os.path.exists(CSC_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % CSC_HEADER)
 with open(CSC_HEADER) as _f:
     csc_consts, csc_structs, csc_signatures = parse(_f.read())
+
+# the twelfth public header (PT-v2m1: the logits stage with GroupedLinear and the position multiplier), likewise
+V2M1_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_v2m1_hip.h")
+if not os.path.exists(V2M1_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % V2M1_HEADER)
+with open(V2M1_HEADER) as _f:
+    v2m1_consts, v2m1_structs, v2m1_signatures = parse(_f.read())

@@ -46,6 +46,8 @@ EXPECTED_ST_ABI = 1
 EXPECTED_INSEVAL_ABI = 1
 # the same for include/ptv2_csc_hip.h and ptv2_csc_abi_version() (ao_amd/csrc/msc_csc.hip)
 EXPECTED_CSC_ABI = 1
+# the same for include/ptv2_v2m1_hip.h and ptv2_v2m1_abi_version() (ao_amd/csrc/gva_mul.hip)
+EXPECTED_V2M1_ABI = 1
 
 
 def build(verbose=False):
@@ -65,7 +67,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures, _abi.pp2s_signatures,
                       _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures, _abi.msc_signatures,
-                      _abi.st_signatures, _abi.inseval_signatures, _abi.csc_signatures):
+                      _abi.st_signatures, _abi.inseval_signatures, _abi.csc_signatures, _abi.v2m1_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -127,6 +129,10 @@ def lib():
         if have != EXPECTED_CSC_ABI:
             raise RuntimeError("ao_amd: %s has csc ABI version %d, the python side expects %d -- stale build; rebuild with "
                                "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_CSC_ABI))
+        have = handle.ptv2_v2m1_abi_version()
+        if have != EXPECTED_V2M1_ABI:
+            raise RuntimeError("ao_amd: %s has v2m1 ABI version %d, the python side expects %d -- stale build; rebuild with "
+                               "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_V2M1_ABI))
         for which, name in enumerate(("ptv1_params", "ptv1_norms", "ptv1_grads")):
             if handle.ptv2_ptv1_struct_bytes(which) != ctypes.sizeof(_abi.ptv1_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

@@ -5,10 +5,12 @@ from .model import (  # noqa: F401
     Decoder,
     Encoder,
     GridPool,
+    GroupedLinear,
     GroupedVectorAttention,
     GVAPatchEmbed,
     PointBatchNorm,
     PointTransformerV2,
+    PointTransformerV2M1,
     UnpoolWithSkip,
     build_from_cfg,
 )

@@ -103,8 +103,9 @@ class _Plan:
         b0 = self.bns[0]
         # static_core: what the whole-model runtime needs of a Block (it implements enable_checkpoint itself,
         # ptv2_model.checkpoint); static_ok: the per-Block launchers, which leave checkpointing to torch
+        # (a GroupedLinear in weight_encoding -- PT-v2m1 -- is a (1, C) weight in a (G, C) slot: never native)
         self.static_core = (
-            not a.pe_multiplier and a.pe_bias
+            not a.pe_multiplier and a.pe_bias and isinstance(a.weight_encoding[0], torch.nn.Linear)
             and all(p is None or (p.dtype == torch.float32 and p.is_cuda and p.is_contiguous()) for p in self.params)
             and all(bn.momentum is not None and bn.affine and bn.eps == b0.eps and bn.momentum == b0.momentum
                     and (bn.running_mean is None) == (b0.running_mean is None) for bn in self.bns))

@@ -22,6 +22,16 @@ computed once per table by a HIP reduction.  BN_w statistics come out of the log
 channel sums.  All dense products (kW, qW, M, the grouped A x Wp2 product) stay in torch on rocBLAS;
 autograd composes the two HIP stages (`logits`, `aggregate`) with them, which also yields the exact
 BatchNorm backward through the batch statistics.
+
+PT-v2m1 (GroupedLinear weight w (C) as weight_encoding[0], pe_multiplier=True; point_transformer_v2m1_origin.py:141-159) puts
+the position multiplier pem = Pm Wm2^T + bm2, Pm = ReLU(pos a_m^T + b_m), between key[idx] - q and that layer:
+
+  W1[n,s,g]  = sum_{c in g} w[c] (k[idx[n,s],c]*mask - q[n,c]) pem[n,s,c] + P M + cW,
+               M[c',g] = sum_{c in g} w[c] Wp2[c,c'], cW[g] = sum_{c in g} w[c] bp2[c]
+
+kW[idx] - qW no longer factors out, so this W1 comes from a stage of its own (`logits_mul`: ao_amd/csrc/gva_mul.hip, pem on the
+matrix cores per tile of 16 slots, never stored); everything behind W1 is unchanged, because value + peb does not see the
+multiplier.
 """
 import ctypes
 import os
@@ -66,6 +76,10 @@ class _HipImpl:
     @staticmethod
     def logits(kW, qW, a, b, M, cW, coord, idx):
         return _Logits.apply(kW, qW, a, b, M, cW, coord, idx)
+
+    @staticmethod
+    def logits_mul(key, query, w, a_m, b_m, Wm2, bm2, a, b, M, cW, coord, idx):
+        return _LogitsMul.apply(key, query, w, a_m, b_m, Wm2, bm2, a, b, M, cW, coord, idx)
 
     @staticmethod
     def aggregate(W1, sc, sh, Ww2, bw2, v, a, b, coord, idx):
@@ -208,6 +222,58 @@ class _Logits(torch.autograd.Function):
         return gkW, gqW, ga, gb, gM, gcW, None, None
 
 
+class _LogitsMul(torch.autograd.Function):
+    """W1 (N,K,G) of PT-v2m1 (GroupedLinear weight w, position multiplier) and its per-channel sums: the formulas of
+    include/ptv2_v2m1_hip.h (ao_amd/csrc/gva_mul.hip).  pem is formed again by the backward; what is saved is O(N C + N K G)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, key, query, w, a_m, b_m, Wm2, bm2, a, b, M, cW, coord, idx):
+        _lib.require_cuda(key, query, w, a_m, b_m, Wm2, bm2, a, b, M, cW, coord, idx)
+        key, query, w, a_m, b_m, Wm2, bm2, a, b, M, cW = (_f32c(t) for t in (key, query, w, a_m, b_m, Wm2, bm2, a, b, M, cW))
+        n, k = idx.shape
+        c, g = M.shape
+        dev = key.device
+        W1 = torch.empty((n, k, g), dtype=torch.float32, device=dev)
+        T1 = torch.empty(g, dtype=torch.float64, device=dev)
+        T2 = torch.empty(g, dtype=torch.float64, device=dev)
+        L = _lib.lib()
+        ws = _lib.workspace(L.gva_mul_workspace_bytes(n, k, c, g), dev)
+        rc = L.gva_mul_logits_forward_hip_launcher(
+            n, k, c, g, key.data_ptr(), query.data_ptr(), w.data_ptr(), a_m.data_ptr(), b_m.data_ptr(), Wm2.data_ptr(),
+            bm2.data_ptr(), a.data_ptr(), b.data_ptr(), M.data_ptr(), cW.data_ptr(), coord.data_ptr(), idx.data_ptr(),
+            W1.data_ptr(), T1.data_ptr(), T2.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "gva_mul_logits_forward_hip_launcher")
+        inv_ptr, inv_rows = inverse_table(idx) if any(ctx.needs_input_grad) else (None, None)
+        ctx.save_for_backward(key, query, w, a_m, b_m, Wm2, bm2, a, b, M, coord, idx, W1, inv_ptr, inv_rows)
+        return W1, T1, T2
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, gW1, gT1, gT2):
+        key, query, w, a_m, b_m, Wm2, bm2, a, b, M, coord, idx, W1, inv_ptr, inv_rows = ctx.saved_tensors
+        n, k = idx.shape
+        c, g = M.shape
+        dev = W1.device
+        gW1 = torch.zeros_like(W1) if gW1 is None else gW1.contiguous()
+        gT1 = torch.zeros(g, dtype=torch.float64, device=dev) if gT1 is None else gT1.contiguous()
+        gT2 = torch.zeros(g, dtype=torch.float64, device=dev) if gT2 is None else gT2.contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        outs = dict(g_key=new(n, c), g_query=new(n, c), g_w=new(c), g_Wm2=new(c, c), g_bm2=new(c), g_a_m=new(c, 3), g_b_m=new(c),
+                    g_a=new(c, 3), g_b=new(c), g_M=new(c, g), g_cW=new(g))
+        L = _lib.lib()
+        ws = _lib.workspace(L.gva_mul_workspace_bytes(n, k, c, g), dev)
+        rc = L.gva_mul_logits_backward_hip_launcher(
+            n, k, c, g, key.data_ptr(), query.data_ptr(), w.data_ptr(), a_m.data_ptr(), b_m.data_ptr(), Wm2.data_ptr(),
+            bm2.data_ptr(), a.data_ptr(), b.data_ptr(), M.data_ptr(), coord.data_ptr(), idx.data_ptr(), W1.data_ptr(),
+            gW1.data_ptr(), gT1.data_ptr(), gT2.data_ptr(), inv_ptr.data_ptr(), inv_rows.data_ptr(),
+            *(t.data_ptr() for t in outs.values()), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "gva_mul_logits_backward_hip_launcher")
+        o = outs
+        return (o["g_key"], o["g_query"], o["g_w"], o["g_a_m"], o["g_b_m"], o["g_Wm2"], o["g_bm2"], o["g_a"], o["g_b"], o["g_M"],
+                o["g_cW"], None, None)
+
+
 class _Aggregate(torch.autograd.Function):
     """(out_v (N,C), A (N,G,C), sw (N,G)); see module docstring."""
 
@@ -277,6 +343,20 @@ def dropout_supported(channels, groups, k):
     the backward needs the fused point kernel (ao_amd/csrc/gva_bwd_point.hip: the five (G, C) instances, k <= 16)."""
     return ((groups, channels) in ((6, 48), (12, 96), (24, 192), (48, 384), (64, 512)) and k & (k - 1) == 0 and 2 <= k <= 16
             and not os.environ.get("AO_AMD_BWD_STAGED"))
+
+
+def mul_supported(channels, groups, n, k):
+    """Shapes of the multiplier logits stage (include/ptv2_v2m1_hip.h) among those the aggregate stage takes; anything else
+    runs the literal op sequence.  MUL_LITERAL_SHAPES: level shapes at which the literal sequence measured faster on the MI355X
+     and therefore keeps the default path."""
+    return ((channels, groups) in ((48, 6), (96, 12), (192, 24), (384, 48), (512, 64)) and k & (k - 1) == 0 and 2 <= k <= 64
+            and n >= 1 and n * k < 2 ** 31 and (channels, groups) not in MUL_LITERAL_SHAPES)
+
+
+# (384, 48): 3.68 ms fused against 3.17 ms literal for one Block forward + backward at 903 points; (512, 64): 12.26 against 3.21 ms
+# (profiles/ptv2m1_bench.jsonl): a tile's three (16 x C) x (C x C) products run on ONE wavefront, and a few hundred tiles leave
+# most of the GPU idle.  The launchers take both shapes (tests/test_gpu_ptv2m1_stage.py); the default path does not.
+MUL_LITERAL_SHAPES = ((384, 48), (512, 64))
 
 
 def _track(bn, training):
@@ -589,57 +669,33 @@ def _bn_update(bn, mean, var_biased, rows):
         bn.running_var.mul_(1 - m).add_(unbiased.detach().to(bn.running_var.dtype), alpha=m)
 
 
-def grouped_vector_attention(mod, query, key, value, coord, reference_index, impl=None):
-    """mod: GroupedVectorAttention (pe_bias=True, pe_multiplier=False); query/key/value (N,C) are the outputs
-    of mod.linear_q / linear_k / linear_v.  Returns (N,C).  `impl` swaps the three device stages
-    (tests pass a torch restatement to check this host logic on CPU)."""
-    if impl is None and os.environ.get("AO_AMD_GVA", "fused") != "staged":
-        return _block_call(mod, query.float(), key.float(), value.float(), coord.contiguous(),
-                           reference_index.contiguous())
-    impl = impl or _HipImpl
+def _fold_p(impl, f, mod, seq, mu, cov, rows, training_stats):
+    """(a (C,3), b (C)) of P = ReLU(pos a^T + b) for seq = Sequential(Linear(3,C), PointBatchNorm, ReLU, ...): the BatchNorm
+    folded into an affine map of pos (linear_p_bias, and linear_p_multiplier of PT-v2m1: the same pos moments)."""
+    lin, bn = seq[0], seq[1].norm
+    if hasattr(impl, "fold_p"):
+        return impl.fold_p(lin, bn, mu, cov, rows, training_stats)
+    Wp1, bp1 = f(lin.weight), f(lin.bias)
+    if training_stats:
+        mu32, cov32 = f(mu), f(cov)
+        mean_p = Wp1 @ mu32 + bp1
+        var_p = ((Wp1 @ cov32) * Wp1).sum(1).clamp_min(0)
+        if mod.training:
+            _bn_update(bn, mean_p, var_p, rows)
+    else:
+        mean_p, var_p = f(bn.running_mean), f(bn.running_var)
+    scale_p = f(bn.weight) * torch.rsqrt(var_p + bn.eps)
+    return Wp1 * scale_p.unsqueeze(1), (bp1 - mean_p) * scale_p + f(bn.bias)
+
+
+def _attend(impl, f, mod, W1, T1, T2, value, a, b, Wp2, bp2, coord, idx):
+    """BN_w from the per-channel sums of W1, softmax over the neighbours, aggregation of v and of the folded positional
+    bias: what follows the logits stage, whichever stage formed W1."""
     C, G = mod.embed_channels, mod.groups
     I = C // G
-    idx = reference_index.contiguous()
     N, K = idx.shape
     rows = N * K
-    coord = coord.contiguous()
-    # (a float64 module stays float64: the torch restatement of the stages then serves as a high-precision reference)
-    f = (lambda t: t) if query.dtype == torch.float64 else (lambda t: t.float())
-    query, key, value = f(query), f(key), f(value)
-    lin_p1, bn_p, lin_p2 = mod.linear_p_bias[0], mod.linear_p_bias[1].norm, mod.linear_p_bias[3]
-    lin_w1, bn_w, lin_w2 = mod.weight_encoding[0], mod.weight_encoding[1].norm, mod.weight_encoding[3]
-    training_stats = mod.training or not bn_p.track_running_stats or bn_p.running_mean is None
-
-    # -- BN_p folded into an affine map of pos: P = ReLU(pos a^T + b) -----------------------------
-    Wp1, bp1 = f(lin_p1.weight), f(lin_p1.bias)
-    mu = cov = None
-    if training_stats:
-        mu, cov = _pos_moments(impl, coord, idx)
-    if hasattr(impl, "fold_p"):
-        a, b = impl.fold_p(lin_p1, bn_p, mu, cov, rows, training_stats)
-    else:
-        if training_stats:
-            mu32, cov32 = f(mu), f(cov)
-            mean_p = Wp1 @ mu32 + bp1
-            var_p = ((Wp1 @ cov32) * Wp1).sum(1).clamp_min(0)
-            if mod.training:
-                _bn_update(bn_p, mean_p, var_p, rows)
-        else:
-            mean_p, var_p = f(bn_p.running_mean), f(bn_p.running_var)
-        scale_p = f(bn_p.weight) * torch.rsqrt(var_p + bn_p.eps)
-        a = Wp1 * scale_p.unsqueeze(1)
-        b = (bp1 - mean_p) * scale_p + f(bn_p.bias)
-
-    # -- logits: W1 = kW[idx] - qW + P M + cW ------------------------------------------------------
-    Wp2, bp2 = f(lin_p2.weight), f(lin_p2.bias)
-    Ww1, bw1 = f(lin_w1.weight), f(lin_w1.bias)
-    M = Wp2.t() @ Ww1.t()                      # (C,G): M[c',g] = sum_c Wp2[c,c'] Ww1[g,c]
-    cW = torch.addmv(bw1, Ww1, bp2)
-    kW = skinny_linear(key, Ww1)
-    qW = skinny_linear(query, Ww1)
-    W1, T1, T2 = impl.logits(kW, qW, a, b, M, cW, coord, idx)
-
-    # -- BN_w from the per-channel sums of W1 --------------------------------------------------------
+    bn_w, lin_w2 = mod.weight_encoding[1].norm, mod.weight_encoding[3]
     train_w = mod.training or not bn_w.track_running_stats
     if hasattr(impl, "fold_w"):
         sc, sh = impl.fold_w(T1, T2, bn_w, rows, train_w)
@@ -654,10 +710,61 @@ def grouped_vector_attention(mod, query, key, value, coord, reference_index, imp
         sc64 = bn_w.weight.double() * torch.rsqrt(var_w + bn_w.eps)
         sh64 = bn_w.bias.double() - mean_w * sc64
         sc, sh = f(sc64), f(sh64)
-
-    # -- softmax over neighbours, aggregation of v and of the folded positional bias ---------------
     out_v, A, sw = impl.aggregate(W1, sc, sh, f(lin_w2.weight), f(lin_w2.bias), value, a, b, coord, idx)
     if hasattr(impl, "project"):
         return impl.project(A, Wp2, bp2, sw, out_v)
     peb = torch.einsum("ngc,gic->ngi", A, Wp2.view(G, I, C))
     return out_v + peb.reshape(N, C) + (sw.unsqueeze(-1) * bp2.view(1, G, I)).reshape(N, C)
+
+
+def grouped_vector_attention(mod, query, key, value, coord, reference_index, impl=None):
+    """mod: GroupedVectorAttention with pe_bias=True; query/key/value (N,C) are the outputs of mod.linear_q / linear_k /
+    linear_v.  Returns (N,C).  pe_multiplier=False with a Linear weight encoding (PT-v2m2): the fused Block call, or the
+    staged composition below.  pe_multiplier=True with a GroupedLinear weight encoding (PT-v2m1): the staged composition with
+    the multiplier logits stage (`logits_mul`) in the place of `logits`; fold_p, fold_w, aggregate and project are the same,
+    because value + peb does not see the multiplier.  `impl` swaps the device stages (tests pass a torch restatement to check
+    this host logic on CPU)."""
+    mul = bool(mod.pe_multiplier)
+    if impl is None and not mul and os.environ.get("AO_AMD_GVA", "fused") != "staged":
+        return _block_call(mod, query.float(), key.float(), value.float(), coord.contiguous(),
+                           reference_index.contiguous())
+    impl = impl or _HipImpl
+    C, G = mod.embed_channels, mod.groups
+    I = C // G
+    idx = reference_index.contiguous()
+    N, K = idx.shape
+    rows = N * K
+    coord = coord.contiguous()
+    # (a float64 module stays float64: the torch restatement of the stages then serves as a high-precision reference)
+    f = (lambda t: t) if query.dtype == torch.float64 else (lambda t: t.float())
+    query, key, value = f(query), f(key), f(value)
+    bn_p, lin_p2 = mod.linear_p_bias[1].norm, mod.linear_p_bias[3]
+    lin_w1 = mod.weight_encoding[0]
+    training_stats = mod.training or not bn_p.track_running_stats or bn_p.running_mean is None
+
+    # -- BN_p folded into an affine map of pos: P = ReLU(pos a^T + b) -----------------------------
+    mu = cov = None
+    if training_stats:
+        mu, cov = _pos_moments(impl, coord, idx)
+    a, b = _fold_p(impl, f, mod, mod.linear_p_bias, mu, cov, rows, training_stats)
+    Wp2, bp2 = f(lin_p2.weight), f(lin_p2.bias)
+
+    if mul:
+        # -- logits of PT-v2m1: W1 = GroupedLinear((key[idx] - query) * pem + peb), pem = Pm Wm2^T + bm2 never stored ------
+        if lin_w1.weight.shape != (1, C) or lin_w1.bias is not None:
+            raise RuntimeError("ao_amd: the multiplier logits stage needs a GroupedLinear weight encoding")
+        a_m, b_m = _fold_p(impl, f, mod, mod.linear_p_multiplier, mu, cov, rows, training_stats)
+        lin_m2 = mod.linear_p_multiplier[3]
+        w = f(lin_w1.weight).reshape(C)
+        M = (Wp2 * w.unsqueeze(1)).view(G, I, C).sum(1).t().contiguous()   # (C,G): M[c',g] = sum_{c in g} w[c] Wp2[c,c']
+        cW = (w * bp2).view(G, I).sum(1)
+        W1, T1, T2 = impl.logits_mul(key, query, w, a_m, b_m, f(lin_m2.weight), f(lin_m2.bias), a, b, M, cW, coord, idx)
+    else:
+        # -- logits: W1 = kW[idx] - qW + P M + cW ------------------------------------------------------
+        Ww1, bw1 = f(lin_w1.weight), f(lin_w1.bias)
+        M = Wp2.t() @ Ww1.t()                      # (C,G): M[c',g] = sum_c Wp2[c,c'] Ww1[g,c]
+        cW = torch.addmv(bw1, Ww1, bp2)
+        kW = skinny_linear(key, Ww1)
+        qW = skinny_linear(query, Ww1)
+        W1, T1, T2 = impl.logits(kW, qW, a, b, M, cW, coord, idx)
+    return _attend(impl, f, mod, W1, T1, T2, value, a, b, Wp2, bp2, coord, idx)

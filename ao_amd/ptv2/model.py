@@ -20,6 +20,7 @@ Every stage module also answers the reference's own `forward` signature -- `Grid
 the same kernels, so code that drives a stage directly keeps working; `PointTransformerV2.forward` itself goes
 through the geometry plan (`pool` / `unpool` methods) so that nothing geometric is recomputed.
 """
+import math
 import os
 
 import torch
@@ -64,6 +65,32 @@ class LinBnRelu(nn.Sequential):
 
 def _lin_bn_relu(cin, cout, bias):
     return LinBnRelu(cin, cout, bias)
+
+
+class GroupedLinear(nn.Module):
+    """PT-v2m1's first layer of weight_encoding (reference point_transformer_v2m1_origin.py:24-62): one weight per input
+    channel, summed per group -- out[..., g] = sum_{c in g} x[..., c] weight[0, c].  State-dict key and shape are the
+    reference's: `weight`, (1, in_features); there is no bias."""
+    __constants__ = ["in_features", "out_features", "groups"]
+    bias = None  # (what a Linear in this slot would carry: code that walks a Block's parameters reads None)
+
+    def __init__(self, in_features, out_features, groups, device=None, dtype=None):
+        super().__init__()
+        self.in_features, self.out_features, self.groups = in_features, out_features, groups
+        assert in_features % groups == 0
+        assert out_features % groups == 0
+        assert out_features == groups  # one output per group, as the reference
+        self.weight = nn.Parameter(torch.empty((1, in_features), device=device, dtype=dtype))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+
+    def forward(self, input):
+        return (input * self.weight).reshape(list(input.shape[:-1]) + [self.groups, input.shape[-1] // self.groups]).sum(-1)
+
+    def extra_repr(self):
+        return "in_features={}, out_features={}, groups={}".format(self.in_features, self.out_features, self.groups)
 
 
 class GroupedVectorAttention(nn.Module):
@@ -123,12 +150,20 @@ class GroupedVectorAttention(nn.Module):
         # attention dropout: inside the fused kernels (mode "fused": one native call per direction); the staged composition
         # (one autograd node per stage) has no place for the mask and falls back to the literal op sequence
         dropping = self.attn_drop_rate > 0.0 and self.training
-        fusable = self.pe_bias and not self.pe_multiplier and (not dropping or mode == "fused")
+        grouped = isinstance(self.weight_encoding[0], GroupedLinear)
+        fusable = self.pe_bias and not self.pe_multiplier and not grouped and (not dropping or mode == "fused")
         if mode in ("fused", "staged") and fusable:
             from . import gva
 
             if gva.supported(self.embed_channels, self.groups, reference_index.shape[1]) and (
                     not dropping or gva.dropout_supported(self.embed_channels, self.groups, reference_index.shape[1])):
+                return gva.grouped_vector_attention(self, query, key, value, coord, reference_index)
+        # PT-v2m1: GroupedLinear + position multiplier -- the staged composition around the multiplier logits stage
+        # (ao_amd/csrc/gva_mul.hip); attention dropout in training takes the literal sequence, as the staged composition does
+        if mode in ("fused", "staged") and self.pe_bias and self.pe_multiplier and grouped and not dropping:
+            from . import gva
+
+            if gva.mul_supported(self.embed_channels, self.groups, reference_index.shape[0], reference_index.shape[1]):
                 return gva.grouped_vector_attention(self, query, key, value, coord, reference_index)
         return self.gva_unfused(query, key, value, coord, reference_index)
 
@@ -501,6 +536,34 @@ class PointTransformerV2(nn.Module):
         return self.seg_head(feat)
 
 
+def use_grouped_linear(module):
+    """Replace the first layer of weight_encoding of every GroupedVectorAttention under `module` by a GroupedLinear: what
+    separates PT-v2m1 from PT-v2m2 (reference point_transformer_v2m1_origin.py:133).  Returns `module`."""
+    for m in module.modules():
+        if isinstance(m, GroupedVectorAttention):
+            m.weight_encoding[0] = GroupedLinear(m.embed_channels, m.groups, m.groups)
+    return module
+
+
+class PointTransformerV2M1(PointTransformerV2):
+    """Registry name "PT-v2m1" (reference point_transformer_v2m1_origin.py:485): PT-v2m2 with GroupedLinear as the first layer
+    of every weight_encoding.  Constructor keywords and state-dict keys are the reference's.  A Block with a GroupedLinear
+    never enters the native Block / model runtimes (block._Plan.static_core): the network runs stage by stage, its attention
+    through ao_amd.ptv2.gva (pe_multiplier=True, the reference configs' setting: the fused multiplier logits stage)."""
+
+    def __init__(self, in_channels, num_classes, patch_embed_depth=1, patch_embed_channels=48, patch_embed_groups=6,
+                 patch_embed_neighbours=8, enc_depths=(2, 2, 6, 2), enc_channels=(96, 192, 384, 512),
+                 enc_groups=(12, 24, 48, 64), enc_neighbours=(16, 16, 16, 16), dec_depths=(1, 1, 1, 1),
+                 dec_channels=(48, 96, 192, 384), dec_groups=(6, 12, 24, 48), dec_neighbours=(16, 16, 16, 16),
+                 grid_sizes=(0.06, 0.12, 0.24, 0.48), attn_qkv_bias=True, pe_multiplier=False, pe_bias=True,
+                 attn_drop_rate=0.0, drop_path_rate=0, enable_checkpoint=False, unpool_backend="map"):
+        super().__init__(in_channels, num_classes, patch_embed_depth, patch_embed_channels, patch_embed_groups,
+                         patch_embed_neighbours, enc_depths, enc_channels, enc_groups, enc_neighbours, dec_depths, dec_channels,
+                         dec_groups, dec_neighbours, grid_sizes, attn_qkv_bias, pe_multiplier, pe_bias, attn_drop_rate,
+                         drop_path_rate, enable_checkpoint, unpool_backend)
+        use_grouped_linear(self)
+
+
 def parallel_ddp_ignore(module, prefix):
     """The `_ddp_params_and_buffers_to_ignore` list of `module` (PointTransformerV2 itself, prefix "", or a segmentor that holds
     it as `backbone`, prefix "backbone."): every backbone parameter but the smallest one, when the native runtime will average
@@ -539,7 +602,8 @@ MODEL_TYPE = "PT-v2m2"
 
 
 def build_from_cfg(cfg):
-    """cfg: the `backbone=dict(type="PT-v2m2", ...)` dict of the reference configs."""
+    """cfg: the `backbone=dict(type="PT-v2m2", ...)` dict of the reference configs ("PT-v2m1": PointTransformerV2M1)."""
     cfg = dict(cfg)
-    assert cfg.pop("type", MODEL_TYPE) == MODEL_TYPE
-    return PointTransformerV2(**cfg)
+    kind = cfg.pop("type", MODEL_TYPE)
+    assert kind in (MODEL_TYPE, "PT-v2m1"), kind
+    return (PointTransformerV2 if kind == MODEL_TYPE else PointTransformerV2M1)(**cfg)

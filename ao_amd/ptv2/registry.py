@@ -33,7 +33,7 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, H
     segmentor and `Criteria` then builds it from the same config entry; with TEST (pointcept/engines/test.py:26) the whole-scene
     tester of ao_amd/ptv2/tester.py under "SemSegTester", which `test = dict(type="SemSegTester")` then resolves to.  Every
     registry may be omitted.  MODELS also receives
-    CACSegmentor under "CAC-v1m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", PointGroup under "PG-v1m1", MaskedSceneContrast
+    CACSegmentor under "CAC-v1m1", PointTransformerV2M1 under "PT-v2m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", PointGroup under "PG-v1m1", MaskedSceneContrast
     under "MSC-v1m1", MaskedSceneContrastCSC under "MSC-v1m2" and StratifiedTransformer under "ST-v1m2" and "STv1m2"; the returned
     list of names leaves those entries out (it predates them).  With HOOKS (pointcept/engines/hooks/builder.py) the instance
     evaluator of ao_amd/pointgroup/evaluate.py is filed under "InsSegEvaluator", likewise not listed."""
@@ -49,6 +49,10 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, H
             done.append(name)
         # (filed under MODELS as well, but not listed in the return value: callers compare that list with the names above)
         _register(MODELS, CACSegmentor, "CAC-v1m1", force)
+        # PT-v2m1 (GroupedLinear + position multiplier), likewise filed and not listed
+        from .model import PointTransformerV2M1
+
+        _register(MODELS, PointTransformerV2M1, "PT-v2m1", force)
         # Point Transformer V1 (ao_amd/ptv1), likewise filed and not listed
         from ..ptv1 import PointTransformerSeg26, PointTransformerSeg38, PointTransformerSeg50
 

@@ -5,7 +5,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .model import PointTransformerV2
+from .model import PointTransformerV2, build_from_cfg
 
 S3DIS_BACKBONE = dict(  # configs/s3dis/semseg-pt-v2m2-0-base.py:12-36
     in_channels=6, num_classes=13, patch_embed_depth=2, patch_embed_channels=48, patch_embed_groups=6,
@@ -124,8 +124,8 @@ class DefaultSegmentor(nn.Module):
 
     def __init__(self, backbone=None, criteria=None, ignore_index=-1):
         super().__init__()
-        self.backbone = backbone if isinstance(backbone, nn.Module) else PointTransformerV2(
-            **{k: v for k, v in dict(backbone).items() if k != "type"})
+        # (a config dict: `type` "PT-v2m2", the default, or "PT-v2m1")
+        self.backbone = backbone if isinstance(backbone, nn.Module) else build_from_cfg(backbone)
         self._criteria = _parse_criteria(criteria, ignore_index)
         self.ignore_index = next((i for _, i, lov in self._criteria if lov is None), ignore_index)
         self.criteria = nn.CrossEntropyLoss(ignore_index=self.ignore_index)  # kept for state / introspection parity
