@@ -22,6 +22,17 @@
 
 static inline int divup(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Workgroups of `kernel` the current device holds at once: occupancy per compute unit x compute units.  A failing (or
+// non-positive) occupancy query counts as occ_fallback, a failing compute-unit query as cu_fallback (256: the MI355X).  Callers
+// raise the kernel's dynamic-LDS limit first where `lds` needs it, and keep their own cache and clamp: those are tuning
+// decisions (gva_bwd_point.hip: launch_bwd_point).
+static inline int ptv2_resident_blocks(const void *kernel, int threads, size_t lds, int occ_fallback, int cu_fallback = 256) {
+    int occ = 0, dev = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) != hipSuccess || occ < 1) occ = occ_fallback;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = cu_fallback;
+    return occ * cus;
+}
+
 // Every region of a workspace / saved buffer / arena starts on a 256-byte boundary.
 static constexpr size_t ptv2_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // Carves consecutive aligned regions out of a caller-owned buffer; p == NULL only measures (off = bytes needed so far).
@@ -208,4 +219,5 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (orig >> 3);
 }
 
+#include "wave_ops.h"
 #include "internal.h"

@@ -361,11 +361,7 @@ int coop_capacity(int RC) {
     if (!cap[slot]) {
         const void *fn = RC == 2 ? (const void *)fps_coop_kernel<2, true> : RC == 4 ? (const void *)fps_coop_kernel<4, true>
                        : RC == 8 ? (const void *)fps_coop_kernel<8, true> : (const void *)fps_coop_kernel<16, true>;
-        int occ = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, FPS_THREADS, 0) != hipSuccess || occ < 1) occ = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 0;
-        cap[slot] = std::max(1, occ * cus);
+        cap[slot] = std::max(1, ptv2_resident_blocks(fn, FPS_THREADS, 0, 1, 0));  // no compute-unit count: capacity 1, not a guess
     }
     return cap[slot];
 }

@@ -36,8 +36,6 @@ __device__ __forceinline__ int lds_slot(int row, int k4) {  // float offset of f
     return row * (KC + 8) + 4 * (k4 ^ (row & (KC == 32 ? 1 : 3)));
 }
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 // up to 3 products of one shape in one launch: independent (blockIdx.y selects X/W/bias/Y: the q, k, v projections
 // of one input) or summed into one output (the reduction runs over the pairs back to back: g_f1 = sum_i gY_i W_i)
 struct GemmMulti {
@@ -58,18 +56,6 @@ struct GemmMulti {
     int bnrelu;
     float *brec;
 };
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {  // all-reduce over the 16 lanes that share lane >> 4
-    v += dpp_mov<0xB1>(v);
-    v += dpp_mov<0x4E>(v);
-    v += dpp_mov<0x141>(v);
-    v += dpp_mov<0x140>(v);
-    return v;
-}
 
 // Epilogue shared by the row GEMM kernels: bias / accumulate / store, then (optionally) the BatchNorm-backward reduce records
 // and the BatchNorm-forward tile statistics of this 64-row block (see GemmMulti).  `sS`: >= 4 * 2 * BN floats of LDS scratch

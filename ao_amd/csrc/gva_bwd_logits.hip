@@ -26,9 +26,6 @@
 
 namespace gva {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v4f mfma4l(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 template <int G, int C, int NW>
 struct LogitsBwdCfg {
     static constexpr int GT = (G + 15) / 16, PW = 4 / NW, CW = C / NW, UT = CW / 16, PER = G + 4;
@@ -161,8 +158,7 @@ __global__ __launch_bounds__(256) void logits_bwd_fused_kernel(int n, int k, con
     int cur = 0;
     for (long long pt = pt0; pt < n; pt += stride, cur ^= 1) {  // (no workgroup barrier inside: trip counts may differ per wavefront)
         const bool act = pt < n;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // record `cur` of this wavefront is in LDS
+        wave_fence_sync();  // record `cur` of this wavefront is in LDS
         // ---- current point: gWt in both layouts from the prefetched rows
         float uA[GT][4], uB[4][GT];
 #pragma unroll
@@ -213,16 +209,16 @@ __global__ __launch_bounds__(256) void logits_bwd_fused_kernel(int n, int k, con
 #pragma unroll
             for (int t = 0; t < GT; ++t) {
                 const float4 m4 = K::HOIST_M ? mreg[u][t] : mcur[t];
-                d = mfma4l(uA[t][0], m4.x, d);
-                d = mfma4l(uA[t][1], m4.y, d);
-                d = mfma4l(uA[t][2], m4.z, d);
-                d = mfma4l(uA[t][3], m4.w, d);
+                d = mfma4(uA[t][0], m4.x, d);
+                d = mfma4(uA[t][1], m4.y, d);
+                d = mfma4(uA[t][2], m4.z, d);
+                d = mfma4(uA[t][3], m4.w, d);
             }
 #pragma unroll
             for (int st = 0; st < 4; ++st) {  // gM (ch, g) += P^T gWt: contraction over the slots s = 4 st + q
                 const float P = pe_act(ab.x, ab.y, ab.z, ab.w, pq[st].x, pq[st].y, pq[st].z);
 #pragma unroll
-                for (int t = 0; t < GT; ++t) accM[u][t] = mfma4l(P, uB[st][t], accM[u][t]);
+                for (int t = 0; t < GT; ++t) accM[u][t] = mfma4(P, uB[st][t], accM[u][t]);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {  // rows s = 4 q + r of column ch
@@ -306,10 +302,7 @@ int launch_logits_bwd_fused(int n, int k, const LogitsIn &I, const LogitsBwdIn &
     static int resident = 0;
     if (!resident) {
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int occ = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kern, 256, lds) != hipSuccess || occ < 1) occ = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = std::max(64, std::min(occ * cus, 512));
+        resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 512));
     }
     const long long groups = ((long long)n + K::PW - 1) / K::PW;
     long long cap = std::min<long long>(resident, (long long)(part_floats_avail / K::REC));
@@ -436,8 +429,7 @@ __global__ __launch_bounds__(256) void logits_bwd_fused6_kernel(int n, const flo
         load_rows(pt + stride);
         const Raw raw_n = load_raw(pt + stride, idx_n);
         idx_n = load_idx(pt + 2 * stride);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // the gWt record and position record `cur` of this wavefront are in LDS
+        wave_fence_sync();  // the gWt record and position record `cur` of this wavefront are in LDS
         // ---- the two operand layouts
         const float uA0 = myRow[l15 * G + q];                       // (slot l15, group q + 4 j)
         const float uA1r = myRow[l15 * G + 4 + (q & 1)];
@@ -456,12 +448,12 @@ __global__ __launch_bounds__(256) void logits_bwd_fused6_kernel(int n, const flo
         for (int u = 0; u < UT; ++u) {
             const float4 ab = abr[u];
             v4f d = (v4f){0.f, 0.f, 0.f, 0.f};
-            d = mfma4l(uA0, mreg[u][0], d);  // D (s, ch) = gWt (s, g) M^T (g, ch)
-            d = mfma4l(uA1, mreg[u][1], d);
+            d = mfma4(uA0, mreg[u][0], d);  // D (s, ch) = gWt (s, g) M^T (g, ch)
+            d = mfma4(uA1, mreg[u][1], d);
 #pragma unroll
             for (int st = 0; st < 4; ++st) {  // gM (ch, g) += P^T gWt: contraction over the slots s = 4 st + q
                 const float P = pe_act(ab.x, ab.y, ab.z, ab.w, pq[st].x, pq[st].y, pq[st].z);
-                accM[u] = mfma4l(P, uB[st], accM[u]);
+                accM[u] = mfma4(P, uB[st], accM[u]);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {  // rows s = 4 q + r of column ch
@@ -473,8 +465,7 @@ __global__ __launch_bounds__(256) void logits_bwd_fused6_kernel(int n, const flo
                 accAB[u].w += gpre;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // every read of the two records is done before they are written again
+        wave_fence_sync();  // every read of the two records is done before they are written again
         myPos[(cur ^ 1) * 16 + l16] = rel_of(raw_n);
     }
 
@@ -517,10 +508,7 @@ int launch_logits_bwd_fused6(int n, const LogitsIn &I, const LogitsBwdIn &X, con
     auto kern = logits_bwd_fused6_kernel<C>;
     static int resident = 0;  // exactly the co-resident workgroups, as launch_logits_bwd_fused
     if (!resident) {
-        int occ = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kern, 256, lds) != hipSuccess || occ < 1) occ = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = std::max(64, std::min(occ * cus, 1024));
+        resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 1024));
     }
     const long long groups = ((long long)n + 3) / 4;
     long long cap = std::min<long long>(resident, (long long)(part_floats_avail / REC));
@@ -640,8 +628,7 @@ __global__ __launch_bounds__(256) void logits_fwd_mfma_kernel(int n, int k, cons
     for (long long base = base0; base < n; base += stride, cur ^= 1) {
         const long long pt = base + p;
         const bool act = pt < n;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_fence_sync();
         const float4 myp = myPos[cur * 16 + l15];  // slot l15 of my point: the A operand's row
         // requests: this point's kW rows and qW row (consumed after the products), the next point's coordinates, ids two ahead
         float kv[FT][4], qv[FT];
@@ -668,7 +655,7 @@ __global__ __launch_bounds__(256) void logits_fwd_mfma_kernel(int n, int k, cons
             const float4 ab = sAB[c0 + 4 * ks + q];
             const float P = pe_act(ab.x, ab.y, ab.z, ab.w, myp.x, myp.y, myp.z);
 #pragma unroll
-            for (int tg = 0; tg < GT; ++tg) acc[tg] = mfma4l(P, mreg[ks][tg], acc[tg]);
+            for (int tg = 0; tg < GT; ++tg) acc[tg] = mfma4(P, mreg[ks][tg], acc[tg]);
         }
         if (NW > 1) {  // channel parts -> LDS, the wavefront that owns a g tile adds them up (fixed order)
 #pragma unroll
@@ -744,10 +731,7 @@ int launch_logits_fwd_mfma(int n, int k, const LogitsIn &I, const LogitsOut &O, 
     static int resident = 0;
     if (!resident) {
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int occ = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kern, 256, lds) != hipSuccess || occ < 1) occ = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = std::max(64, std::min(occ * cus, MAX_BLOCKS));
+        resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), MAX_BLOCKS));
     }
     const long long groups = ((long long)n + PW - 1) / PW;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(groups, resident));

@@ -23,41 +23,9 @@
 
 namespace gva {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// all-reduce over the 16 lanes of a DPP row (lanes that share lane >> 4)
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror
-    return v;
-}
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, dpp_mov<0xB1>(v));
-    v = fmaxf(v, dpp_mov<0x4E>(v));
-    v = fmaxf(v, dpp_mov<0x141>(v));
-    v = fmaxf(v, dpp_mov<0x140>(v));
-    return v;
-}
-
-__host__ __device__ constexpr int ww_pitch(int G) {  // >= G, = 4 mod 16: the 4 lane groups hit disjoint LDS banks
-    int p = G;
-    while (p % 16 != 4) ++p;
-    return p;
-}
-
 template <int G, int C, int NW>
 struct BwdPointCfg {
-    static constexpr int GT = (G + 15) / 16, G16 = GT * 16, GPW = ww_pitch(G), PW = 4 / NW, CW = C / NW, CS = CW / 4,
+    static constexpr int GT = (G + 15) / 16, G16 = GT * 16, GPW = pitch16(G), PW = 4 / NW, CW = C / NW, CS = CW / 4,
                          UT = CW / 16, I = C / G, PF = 4 * C + 3 * G + G * G;
     static constexpr int LT = (GT + NW - 1) / NW;            // group tiles per wave in the j-parallel phase
     static constexpr int NTW = (GT * GT + NW - 1) / NW;      // gWw2 tiles per wave
@@ -270,8 +238,7 @@ __global__ __launch_bounds__(256, G <= 32 ? 2 : 1) void attention_bwd_point_kern
     // one's memory latency: 43 % of the wave cycles were spent parked (profiles/r02_final_sq_counters.jsonl).
     auto point_sync = [&]() {
         if (NW == 1) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            wave_fence_sync();
         } else {
             __syncthreads();
         }
@@ -755,7 +722,7 @@ __global__ __launch_bounds__(256) void attention_softmax_point_kernel(int n, int
                                                                       const float *__restrict__ bw2,
                                                                       const int *__restrict__ idx, float *__restrict__ w,
                                                                       float *__restrict__ sw, PtvDrop drop) {
-    constexpr int GT = (G + 15) / 16, G16 = GT * 16, GPW = ww_pitch(G);
+    constexpr int GT = (G + 15) / 16, G16 = GT * 16, GPW = pitch16(G);
     __shared__ __attribute__((aligned(16))) float sWw[G16 * GPW];
     __shared__ __attribute__((aligned(16))) float sBw[G16], sSc[G16], sSh[G16];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1132,10 +1099,7 @@ int launch_bwd_point(int n, int k, const AttnIn &I, const AttnBwdIn &X, const At
     int *resident = resident_of[dropping];
     if (!resident[local]) {
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int occ = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kern, 256, lds) != hipSuccess || occ < 1) occ = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident[local] = std::max(64, std::min(occ * cus, 512));
+        resident[local] = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 512));
     }
     const long long cap = resident[local];
     const long long groups = ((long long)n + K::PW - 1) / K::PW;

@@ -26,55 +26,10 @@
 
 namespace gva {
 
-typedef float bt_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bt_v4f bt_mfma(float a, float b, bt_v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-template <int CTRL>
-__device__ __forceinline__ float bt_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float bt_row16_sum(float v) {
-    v += bt_dpp<0xB1>(v);
-    v += bt_dpp<0x4E>(v);
-    v += bt_dpp<0x141>(v);
-    v += bt_dpp<0x140>(v);
-    return v;
-}
-__device__ __forceinline__ float bt_row16_max(float v) {
-    v = fmaxf(v, bt_dpp<0xB1>(v));
-    v = fmaxf(v, bt_dpp<0x4E>(v));
-    v = fmaxf(v, bt_dpp<0x141>(v));
-    v = fmaxf(v, bt_dpp<0x140>(v));
-    return v;
-}
-// LDS hand-off inside a wavefront: its LDS operations complete in order once counted down; the compiler must not move LDS
-// accesses across.  (A wavefront-scope fence also waits for the wavefront's GLOBAL stores -- vmcnt(0): ~2 us per point behind
-// the gW1 stores of the tail.)
-__device__ __forceinline__ void bt_wave_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-// v + the same lane of the other quarters (lane ^ 16, then lane ^ 32) without the LDS crossbar: gfx950 swaps rows / halves
-__device__ __forceinline__ float bt_quarter_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    const float h = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(h), __float_as_uint(h), false, false);
-    return __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
-}
-__host__ __device__ constexpr int bt_ww_pitch(int G) {  // >= G, = 4 mod 16
-    int p = G;
-    while (p % 16 != 4) ++p;
-    return p;
-}
-__host__ __device__ constexpr int bt_point_pitch(int G, int GP) {  // >= G GP, = 4 mod 64
-    int p = G * GP;
-    while (p % 64 != 4) p += 4;
-    return p;
-}
-
 template <int G, int C, int TP>
 struct BwdTileCfg {
-    static constexpr int GT = (G + 15) / 16, G16 = GT * 16, GPW = bt_ww_pitch(G), PPW = TP / 4, NCH = C / 16, NGW = G / 4, GP = 20,
-                         PPG = bt_point_pitch(G, GP), PF = 4 * C + 3 * G + G * G,
+    static constexpr int GT = (G + 15) / 16, G16 = GT * 16, GPW = pitch16(G), PPW = TP / 4, NCH = C / 16, NGW = G / 4, GP = 20,
+                         PPG = pitch64(G * GP), PF = 4 * C + 3 * G + G * G,
                          DW = 2 * G16 * 17 > 3 * G + G * G ? 2 * G16 * 17 : 3 * G + G * G;  // a wavefront's transposes, then its record piece
     static_assert((TP == 4 || TP == 8 || TP == 16) && G % 4 == 0 && C == 8 * G && GPW >= G16, "tiles of 8 or 16 points");
     // [sAB 4C] [sWw G16 GPW] [sBw, sSc, sSh 3 G16] [sPos 4 TP 16] [sGo TP C] [sGsw TP G16] [sFinAB 4 x 4C] [sGA 2 TP PPG | sT 4 DW]
@@ -177,24 +132,24 @@ __device__ __forceinline__ void attention_bwd_tile_body(
         }
 #pragma unroll
         for (int tg = 0; tg < GT; ++tg) {
-            bt_v4f z = (bt_v4f){0.f, 0.f, 0.f, 0.f};
+            v4f z = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < GT; ++t) {
                 const float4 w4 = *(const float4 *)(sWw + (16 * tg + l15) * GPW + 16 * t + 4 * q);
-                z = bt_mfma(w4.x, y[t][0], z);
-                z = bt_mfma(w4.y, y[t][1], z);
-                z = bt_mfma(w4.z, y[t][2], z);
-                z = bt_mfma(w4.w, y[t][3], z);
+                z = mfma4(w4.x, y[t][0], z);
+                z = mfma4(w4.y, y[t][1], z);
+                z = mfma4(w4.z, y[t][2], z);
+                z = mfma4(w4.w, y[t][3], z);
             }
             const float4 b4 = *(const float4 *)(sBw + 16 * tg + 4 * q);
             const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float zz = z[r] + bb[r];
-                const float mx = bt_row16_max(zz);
+                const float mx = row16_max(zz);
                 // (hardware exp2 / reciprocal, ~1e-6 relative, as attention_bwd_point_kernel re-evaluates it)
                 const float e = __builtin_amdgcn_exp2f((zz - mx) * 1.44269504088896340736f);
-                const float den = bt_row16_sum(e);
+                const float den = row16_sum(e);
                 sm[i][tg][r] = (16 * tg + 4 * q + r < G) ? e * __builtin_amdgcn_rcpf(den) : 0.f;
                 if (DROP) dr[i][tg][r] = ptv2_drop_factor(drop, ((unsigned long long)pts[i] * 16 + l15) * G + ((16 * tg + 4 * q + r) & 0xffff));
             }
@@ -202,7 +157,7 @@ __device__ __forceinline__ void attention_bwd_tile_body(
     }
     BT_STAMP(3);
     // ---- g_sw of my points (their g_out rows are wave-private so far)
-    bt_wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
         const int p = PPW * wid + i;
@@ -216,12 +171,12 @@ __device__ __forceinline__ void attention_bwd_tile_body(
         }
     }
     // ---- gw^T starts from the v path: <g_out, v[idx[s]]> over the 8 channels of group g = 16 t + 4 q + r, slot s = l15
-    bt_v4f gwT[PPW][GT];
+    v4f gwT[PPW][GT];
 #ifdef BT_SKIP_VPATH
 #pragma unroll
     for (int i = 0; i < PPW; ++i)
 #pragma unroll
-        for (int t = 0; t < GT; ++t) gwT[i][t] = (bt_v4f){0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < GT; ++t) gwT[i][t] = (v4f){0.f, 0.f, 0.f, 0.f};
 #else
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
@@ -292,11 +247,11 @@ __device__ __forceinline__ void attention_bwd_tile_body(
             for (int gi = 0; gi < NGW; ++gi)
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) { wpc[gi][ks] = wpn[gi][ks]; wpn[gi][ks] = wprow[gi][ks][16 * cn]; }
-            bt_v4f da[NGW];
+            v4f da[NGW];
 #pragma unroll
-            for (int gi = 0; gi < NGW; ++gi) da[gi] = bt_mfma(goA[gi][0], wpc[gi][0], (bt_v4f){0.f, 0.f, 0.f, 0.f});
+            for (int gi = 0; gi < NGW; ++gi) da[gi] = mfma4(goA[gi][0], wpc[gi][0], (v4f){0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-            for (int gi = 0; gi < NGW; ++gi) da[gi] = bt_mfma(goA[gi][1], wpc[gi][1], da[gi]);
+            for (int gi = 0; gi < NGW; ++gi) da[gi] = mfma4(goA[gi][1], wpc[gi][1], da[gi]);
             if (4 * q < TP) {
 #pragma unroll
                 for (int gi = 0; gi < NGW; ++gi)
@@ -339,19 +294,19 @@ __device__ __forceinline__ void attention_bwd_tile_body(
 #pragma unroll
         for (int t = 0; t < GT; ++t) {
 #pragma unroll
-            for (int i = 0; i < PPW; ++i) gwT[i][t] = bt_mfma(g4[i][t].x, Pq[i][0], gwT[i][t]);
+            for (int i = 0; i < PPW; ++i) gwT[i][t] = mfma4(g4[i][t].x, Pq[i][0], gwT[i][t]);
 #pragma unroll
-            for (int i = 0; i < PPW; ++i) gwT[i][t] = bt_mfma(g4[i][t].y, Pq[i][1], gwT[i][t]);
+            for (int i = 0; i < PPW; ++i) gwT[i][t] = mfma4(g4[i][t].y, Pq[i][1], gwT[i][t]);
 #pragma unroll
-            for (int i = 0; i < PPW; ++i) gwT[i][t] = bt_mfma(g4[i][t].z, Pq[i][2], gwT[i][t]);
+            for (int i = 0; i < PPW; ++i) gwT[i][t] = mfma4(g4[i][t].z, Pq[i][2], gwT[i][t]);
 #pragma unroll
-            for (int i = 0; i < PPW; ++i) gwT[i][t] = bt_mfma(g4[i][t].w, Pq[i][3], gwT[i][t]);
+            for (int i = 0; i < PPW; ++i) gwT[i][t] = mfma4(g4[i][t].w, Pq[i][3], gwT[i][t]);
         }
 #endif
         // gP (s, c') = w g_A: rows s = 4 q + r, column c' = 16 ck + l15; contraction over the groups, two accumulators per point
-        bt_v4f d0[PPW], d1[PPW];
+        v4f d0[PPW], d1[PPW];
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) d0[i] = d1[i] = (bt_v4f){0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < PPW; ++i) d0[i] = d1[i] = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < GT; ++t)
 #pragma unroll
@@ -366,8 +321,8 @@ __device__ __forceinline__ void attention_bwd_tile_body(
                     for (int i = 0; i < PPW; ++i) {
                         const bool valid = srcv[i] >= 0 && act[i];
                         const float wm = valid ? (DROP ? sm[i][t][r] * dr[DROP ? i : 0][t][r] : sm[i][t][r]) : 0.f;
-                        if (r & 1) d1[i] = bt_mfma(wm, bv[i][t][r], d1[i]);
-                        else d0[i] = bt_mfma(wm, bv[i][t][r], d0[i]);
+                        if (r & 1) d1[i] = mfma4(wm, bv[i][t][r], d1[i]);
+                        else d0[i] = mfma4(wm, bv[i][t][r], d0[i]);
                     }
                 }
             }
@@ -388,8 +343,8 @@ __device__ __forceinline__ void attention_bwd_tile_body(
                 accab.w += gpre;
             }
         }
-        accab.x = bt_quarter_sum(accab.x); accab.y = bt_quarter_sum(accab.y);
-        accab.z = bt_quarter_sum(accab.z); accab.w = bt_quarter_sum(accab.w);
+        accab.x = quarter_sum_swap(accab.x); accab.y = quarter_sum_swap(accab.y);
+        accab.z = quarter_sum_swap(accab.z); accab.w = quarter_sum_swap(accab.w);
         if (q == 0) sFinAB[wid * C + 16 * ck + l15] = accab;
 #endif
     }
@@ -401,13 +356,13 @@ __device__ __forceinline__ void attention_bwd_tile_body(
     // ---- softmax backward, Linear(G,G) backward, the sums over all slots
     float *mGz = sT + wid * DW, *mY = mGz + G16 * 17;
     float tsc[GT][4], tsh[GT][4], gbw[GT][4];
-    bt_v4f accW[GT * GT];
+    v4f accW[GT * GT];
 #pragma unroll
     for (int t = 0; t < GT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) tsc[t][r] = tsh[t][r] = gbw[t][r] = 0.f;
 #pragma unroll
-    for (int e = 0; e < GT * GT; ++e) accW[e] = (bt_v4f){0.f, 0.f, 0.f, 0.f};
+    for (int e = 0; e < GT * GT; ++e) accW[e] = (v4f){0.f, 0.f, 0.f, 0.f};
 #ifndef BT_SKIP_TAIL
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
@@ -427,11 +382,11 @@ __device__ __forceinline__ void attention_bwd_tile_body(
             for (int r = 0; r < 4; ++r) {
                 float gm = valid ? gwT[i][t][r] + gs[r] : 0.f;
                 if (DROP) gm *= dr[DROP ? i : 0][t][r];  // (the weight that reached the aggregation was sm * D)
-                const float dot = bt_row16_sum(sm[i][t][r] * gm);
+                const float dot = row16_sum(sm[i][t][r] * gm);
                 gz[t][r] = act[i] ? sm[i][t][r] * (gm - dot) : 0.f;
             }
         }
-        bt_wave_sync();  // (the previous point's transposes have been read)
+        wave_lds_sync();  // (the previous point's transposes have been read)
 #pragma unroll
         for (int t = 0; t < GT; ++t)
 #pragma unroll
@@ -443,11 +398,11 @@ __device__ __forceinline__ void attention_bwd_tile_body(
         // gy^T (j, s) = Ww2^T gz^T -> gW1, gsc, gsh
 #pragma unroll
         for (int tj = 0; tj < GT; ++tj) {
-            bt_v4f gy = (bt_v4f){0.f, 0.f, 0.f, 0.f};
+            v4f gy = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int tg = 0; tg < GT; ++tg)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) gy = bt_mfma(sWw[(16 * tg + 4 * q + r) * GPW + 16 * tj + l15], gz[tg][r], gy);
+                for (int r = 0; r < 4; ++r) gy = mfma4(sWw[(16 * tg + 4 * q + r) * GPW + 16 * tj + l15], gz[tg][r], gy);
             const float4 s4 = *(const float4 *)(sSc + 16 * tj + 4 * q);
             const float scv[4] = {s4.x, s4.y, s4.z, s4.w};
             float o[4];
@@ -461,14 +416,14 @@ __device__ __forceinline__ void attention_bwd_tile_body(
             if (act[i] && 16 * tj + 4 * q < G) *(float4 *)(gW1 + (pts[i] * 16 + l15) * G + 16 * tj + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
         }
         // gWw2 (g, j) += gz^T y: contraction over the slots, from the transposed tiles
-        bt_wave_sync();
+        wave_lds_sync();
 #pragma unroll
         for (int tg = 0; tg < GT; ++tg)
 #pragma unroll
             for (int tj = 0; tj < GT; ++tj)
 #pragma unroll
                 for (int st = 0; st < 4; ++st)
-                    accW[tg * GT + tj] = bt_mfma(mGz[(16 * tg + l15) * 17 + 4 * st + q], mY[(16 * tj + l15) * 17 + 4 * st + q], accW[tg * GT + tj]);
+                    accW[tg * GT + tj] = mfma4(mGz[(16 * tg + l15) * 17 + 4 * st + q], mY[(16 * tj + l15) * 17 + 4 * st + q], accW[tg * GT + tj]);
     }
 #else
     if (wid == 99) gW1[0] = gwT[0][0][0] + sm[0][0][0] + u1[0][0][0] + mGz[0] + mY[0];
@@ -480,8 +435,8 @@ __device__ __forceinline__ void attention_bwd_tile_body(
 #pragma unroll
     for (int t = 0; t < GT; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { tsc[t][r] = bt_row16_sum(tsc[t][r]); tsh[t][r] = bt_row16_sum(tsh[t][r]); gbw[t][r] = bt_row16_sum(gbw[t][r]); }
-    bt_wave_sync();  // (the last point's transposes have been read: the piece is this wavefront's own)
+        for (int r = 0; r < 4; ++r) { tsc[t][r] = row16_sum(tsc[t][r]); tsh[t][r] = row16_sum(tsh[t][r]); gbw[t][r] = row16_sum(gbw[t][r]); }
+    wave_lds_sync();  // (the last point's transposes have been read: the piece is this wavefront's own)
     {
         float *mine = sT + wid * DW;  // [gsc G][gsh G][gbw2 G][gWw2 G x G]
         if (l15 == 0) {
@@ -579,11 +534,8 @@ static int bwd_tile_full_rounds(int n) {
         using K8 = BwdTileCfg<G, C, 8>;
         using K4 = BwdTileCfg<G, C, 4>;
         const size_t lds = sizeof(float) * std::max(K8::lds_floats, K4::lds_floats);
-        int dev = 0, cus = 0, occ = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
         (void)hipFuncSetAttribute((const void *)attention_bwd_tile_mixed_kernel<G, C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)attention_bwd_tile_mixed_kernel<G, C, false>, 256, lds) != hipSuccess || occ < 1) occ = 2;
-        slots = occ * cus;
+        slots = ptv2_resident_blocks((const void *)attention_bwd_tile_mixed_kernel<G, C, false>, 256, lds, 2);
     }
     static const bool off = ptv2_env_is("AO_AMD_BT_MIXED", '0');
     const int nt8 = (n + 7) / 8, full = nt8 / slots * slots, tail = nt8 - full;

@@ -29,31 +29,6 @@
 
 namespace gva {
 
-typedef float fp_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ fp_v4f fp_mfma(float a, float b, fp_v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-template <int CTRL>
-__device__ __forceinline__ float fp_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float fp_row16_sum(float v) {  // all-reduce over the 16 lanes that share lane >> 4
-    v += fp_dpp<0xB1>(v);
-    v += fp_dpp<0x4E>(v);
-    v += fp_dpp<0x141>(v);
-    v += fp_dpp<0x140>(v);
-    return v;
-}
-__device__ __forceinline__ float fp_row16_max(float v) {
-    v = fmaxf(v, fp_dpp<0xB1>(v));
-    v = fmaxf(v, fp_dpp<0x4E>(v));
-    v = fmaxf(v, fp_dpp<0x141>(v));
-    v = fmaxf(v, fp_dpp<0x140>(v));
-    return v;
-}
-__device__ __forceinline__ void fp_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // stats != NULL: record [blk][2 C] = column sums of `out` over the 64-row block, sums of squares about the block mean
 template <bool STATS>
 __global__ __launch_bounds__(256, 2) void attention_fwd_point6_kernel(
@@ -196,28 +171,28 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_point6_kernel(
         // ---- logits -> softmax over the 16 slots (= the lanes of a DPP row)
         const float y0 = fmaxf(__builtin_fmaf(scr0, g0 >= 0 ? R.u0 : 0.f, shr0), 0.f);
         const float y1 = fmaxf(__builtin_fmaf(scr1, g1 >= 0 ? R.u1 : 0.f, shr1), 0.f);
-        fp_v4f z = (fp_v4f){0.f, 0.f, 0.f, 0.f};
-        z = fp_mfma(wa0, y0, z);
-        z = fp_mfma(wa1, y1, z);
+        v4f z = (v4f){0.f, 0.f, 0.f, 0.f};
+        z = mfma4(wa0, y0, z);
+        z = mfma4(wa1, y1, z);
         float wv[2], so[2];
         {
             const float bb[2] = {bwr0, bwr1};
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 const float zz = z[r] + bb[r];
-                const float mx = fp_row16_max(zz);
+                const float mx = row16_max(zz);
                 // (hardware exp2 / reciprocal, ~1e-6 relative: what the backward's re-evaluation of this softmax uses; the
                 // correctly rounded expf and division are ~20 vector instructions per weight)
                 const float e = __builtin_amdgcn_exp2f((zz - mx) * 1.44269504088896340736f);
-                const float den = fp_row16_sum(e);
+                const float den = row16_sum(e);
                 wv[r] = valid ? e * __builtin_amdgcn_rcpf(den) : 0.f;
-                so[r] = fp_row16_sum(wv[r]);
+                so[r] = row16_sum(wv[r]);
             }
         }
         sWt[wid][(4 * q) * 17 + l15] = wv[0];
         sWt[wid][(4 * q + 1) * 17 + l15] = wv[1];
         if (l15 == 0) { sSw[wid][4 * q] = so[0]; sSw[wid][4 * q + 1] = so[1]; }
-        fp_wave_sync();
+        wave_fence_sync();
         // ---- A = w^T P and V = w^T v[idx]: contraction over the slots, step st of quarter q is slot 4 q + st
         float wA[4];
         float4 pq[4];
@@ -225,17 +200,17 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_point6_kernel(
         for (int st = 0; st < 4; ++st) { wA[st] = sWt[wid][l15 * 17 + 4 * q + st]; pq[st] = sPos[wid][4 * q + st]; }
 #pragma unroll
         for (int u = 0; u < UT; ++u) {
-            fp_v4f accA = (fp_v4f){0.f, 0.f, 0.f, 0.f};
+            v4f accA = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
                 const float P = pe_act(abr[u].x, abr[u].y, abr[u].z, abr[u].w, pq[st].x, pq[st].y, pq[st].z);
-                accA = fp_mfma(wA[st], P, accA);
+                accA = mfma4(wA[st], P, accA);
             }
             const int ch = 16 * u + l15;
             if (g0 >= 0) sA[wid][g0 * AP + ch] = accA[0];
             if (g1 >= 0) sA[wid][g1 * AP + ch] = accA[1];
         }
-        fp_wave_sync();
+        wave_fence_sync();
         // ---- w (16 x 6 floats, contiguous per point) leaves as 24 16-byte pieces gathered from the transposed tile, sw as one
         //      dword per lane (lane % 6): one store instruction each instead of two
         {
@@ -287,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_point6_kernel(
                 st_s2 = __builtin_fmaf(d, d, st_s2);
             }
         }
-        fp_wave_sync();  // the records are rewritten by the next trip
+        wave_fence_sync();  // the records are rewritten by the next trip
         if (STATS && (t & 15) == 15) {  // (uniform over the workgroup: every wavefront runs the same number of trips)
             const long long row0 = (long long)(pt & ~63u);
             const long long left = (long long)n - row0;                   // > 0: the block exists
@@ -340,12 +315,7 @@ int gva_fwd_point_launch(int n, int k, int c, int g, const gva::AttnIn &I, const
     const int nblk = (n + 63) / 64;
     // every workgroup the same number of 64-row blocks, and all of them resident at once
     static int resident = 0;
-    if (!resident) {
-        int occ = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)attention_fwd_point6_kernel<true>, 256, 0) != hipSuccess || occ < 1) occ = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = std::max(64, occ * cus);
-    }
+    if (!resident) resident = std::max(64, ptv2_resident_blocks((const void *)attention_fwd_point6_kernel<true>, 256, 0, 1));
     const int rounds = (nblk + resident - 1) / resident;
     const int grid = (nblk + rounds - 1) / rounds;
     // W1 + idx + coord + v rows (each unique row once) in; w, sw, A, out out

@@ -30,47 +30,10 @@
 
 namespace gva {
 
-typedef float ft_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ ft_v4f ft_mfma(float a, float b, ft_v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-template <int CTRL>
-__device__ __forceinline__ float ft_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float ft_row16_sum(float v) {  // all-reduce over the 16 lanes that share lane >> 4
-    v += ft_dpp<0xB1>(v);
-    v += ft_dpp<0x4E>(v);
-    v += ft_dpp<0x141>(v);
-    v += ft_dpp<0x140>(v);
-    return v;
-}
-__device__ __forceinline__ float ft_row16_max(float v) {
-    v = fmaxf(v, ft_dpp<0xB1>(v));
-    v = fmaxf(v, ft_dpp<0x4E>(v));
-    v = fmaxf(v, ft_dpp<0x141>(v));
-    v = fmaxf(v, ft_dpp<0x140>(v));
-    return v;
-}
-// (LDS hand-off inside a wavefront; a wavefront-scope fence would also wait for the global stores of w / sw: gva_bwd_tile.hip)
-__device__ __forceinline__ void ft_wave_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__host__ __device__ constexpr int ft_ww_pitch(int G) {  // >= G, = 4 mod 16
-    int p = G;
-    while (p % 16 != 4) ++p;
-    return p;
-}
-__host__ __device__ constexpr int ft_point_pitch(int GB, int GP) {  // >= GB GP, = 4 mod 64: the 16 points of a ds_read_b128 on 16 slots
-    int p = GB * GP;
-    while (p % 64 != 4) p += 4;
-    return p;
-}
-
 template <int G, int C, int GB>
 struct FwdTileCfg {
-    static constexpr int GTF = (G + 15) / 16, G16 = GTF * 16, GPW = ft_ww_pitch(G), QB = GB / 4, NGW = GB / 4, OB = 8 * GB,
-                         NCH = C / 16, GP = 20, PP = ft_point_pitch(GB, GP), OP = OB + 4, WT = 16 * 17;
+    static constexpr int GTF = (G + 15) / 16, G16 = GTF * 16, GPW = pitch16(G), QB = GB / 4, NGW = GB / 4, OB = 8 * GB,
+                         NCH = C / 16, GP = 20, PP = pitch64(GB * GP), OP = OB + 4, WT = 16 * 17;
     static_assert(GB % 4 == 0 && GB <= 16 && G % GB == 0 && C == 8 * G && GPW >= G16, "group blocks of 4 q groups");
     static constexpr size_t lds_floats = 4 * (size_t)C + 4 * 256 + 16 * GPW + 16 + 2 * G16 + 16 * WT + 256 + 2 * 16 * PP + 16 * OP;
 };
@@ -175,21 +138,21 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_tile_kernel(
 
     // ---- phase 1: logits -> softmax over the 16 slots (= the lanes of a DPP row) for the rows of this block; the four
     //      points' matrix-instruction chains are interleaved
-    ft_v4f z[4];
+    v4f z[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = (ft_v4f){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 4; ++i) z[i] = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < GTF; ++t) {
         const float4 s4 = *(const float4 *)(sSc + 16 * t + 4 * q), h4 = *(const float4 *)(sSh + 16 * t + 4 * q);
         const float4 w4 = *(const float4 *)(sWw + l15 * GPW + 16 * t + 4 * q);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) z[i] = ft_mfma(w4.x, fmaxf(__builtin_fmaf(s4.x, u[i][t][0], h4.x), 0.f), z[i]);
+        for (int i = 0; i < 4; ++i) z[i] = mfma4(w4.x, fmaxf(__builtin_fmaf(s4.x, u[i][t][0], h4.x), 0.f), z[i]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) z[i] = ft_mfma(w4.y, fmaxf(__builtin_fmaf(s4.y, u[i][t][1], h4.y), 0.f), z[i]);
+        for (int i = 0; i < 4; ++i) z[i] = mfma4(w4.y, fmaxf(__builtin_fmaf(s4.y, u[i][t][1], h4.y), 0.f), z[i]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) z[i] = ft_mfma(w4.z, fmaxf(__builtin_fmaf(s4.z, u[i][t][2], h4.z), 0.f), z[i]);
+        for (int i = 0; i < 4; ++i) z[i] = mfma4(w4.z, fmaxf(__builtin_fmaf(s4.z, u[i][t][2], h4.z), 0.f), z[i]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) z[i] = ft_mfma(w4.w, fmaxf(__builtin_fmaf(s4.w, u[i][t][3], h4.w), 0.f), z[i]);
+        for (int i = 0; i < 4; ++i) z[i] = mfma4(w4.w, fmaxf(__builtin_fmaf(s4.w, u[i][t][3], h4.w), 0.f), z[i]);
     }
     const float4 b4 = *(const float4 *)(sBw + 4 * q);
     const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
@@ -201,16 +164,16 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_tile_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float zz = z[i][r] + bb[r];
-            const float mx = ft_row16_max(zz);
+            const float mx = row16_max(zz);
             // (the correctly rounded expf and division of the staged softmax kernel, in its order: w is bit-identical to it; the
             // ~25 vector instructions per weight do not matter at the deep levels)
             const float e = expf(zz - mx);
-            const float den = ft_row16_sum(e);
+            const float den = row16_sum(e);
             wv[r] = (valid && q < QB) ? e / den : 0.f;
             // attention dropout on the softmax output (gva_common.h: the factor is a hash of the element index, evaluated again
             // by the backward)
             if (DROP) wv[r] *= ptv2_drop_factor(drop, ((unsigned long long)pts[i] * 16 + l15) * G + (g0 + 4 * q + r));
-            so[r] = ft_row16_sum(wv[r]);
+            so[r] = row16_sum(wv[r]);
             sWt[p * WT + (4 * q + r) * 17 + l15] = wv[r];
         }
         if (q < QB) {  // (rows of a clamped point repeat the last point's values)
@@ -222,7 +185,7 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_tile_kernel(
         }
         sPos[p * 16 + l15] = valid ? make_float4(cx[i], cy[i], cz[i], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    ft_wave_sync();  // the records of my 4 points are wave-private until the first chunk barrier
+    wave_lds_sync();  // the records of my 4 points are wave-private until the first chunk barrier
 
     // ---- out_v of my first two points from the rows requested above; the other two points' rows travel through the chunk loop
 #ifndef FT_SKIP_OUTV
@@ -245,13 +208,13 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_tile_kernel(
         }
     const float *wp2row[NGW];
     float4 wpn[NGW];
-    ft_v4f acc[NGW];
+    v4f acc[NGW];
 #pragma unroll
     for (int gi = 0; gi < NGW; ++gi) {
         const int g = wid + 4 * gi;
         wp2row[gi] = Wp2 + (size_t)(o0 + 8 * g + (l15 & 7)) * C + 4 * q;
         wpn[gi] = *(const float4 *)wp2row[gi];
-        acc[gi] = (ft_v4f){0.f, 0.f, 0.f, 0.f};
+        acc[gi] = (v4f){0.f, 0.f, 0.f, 0.f};
     }
 #ifdef FT_SKIP_CHUNKS
     __syncthreads();
@@ -264,14 +227,14 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_tile_kernel(
 #pragma unroll
         for (int gi = 0; gi < NGW; ++gi) { wpc[gi] = wpn[gi]; wpn[gi] = *(const float4 *)(wp2row[gi] + 16 * cn); }
         const float4 ab = sAB[16 * ck + l15];
-        ft_v4f d[4];
+        v4f d[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) d[i] = (ft_v4f){0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < 4; ++i) d[i] = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int st = 0; st < 4; ++st)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                d[i] = ft_mfma(wA[i][st], pe_act(ab.x, ab.y, ab.z, ab.w, pq[i][st].x, pq[i][st].y, pq[i][st].z), d[i]);
+                d[i] = mfma4(wA[i][st], pe_act(ab.x, ab.y, ab.z, ab.w, pq[i][st].x, pq[i][st].y, pq[i][st].z), d[i]);
         if (q < QB) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -288,10 +251,10 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_tile_kernel(
 #pragma unroll
         for (int gi = 0; gi < NGW; ++gi) {
             const float4 bx = *(const float4 *)(buf + l15 * PP + (wid + 4 * gi) * GP + 4 * q);
-            acc[gi] = ft_mfma(wpc[gi].x, bx.x, acc[gi]);
-            acc[gi] = ft_mfma(wpc[gi].y, bx.y, acc[gi]);
-            acc[gi] = ft_mfma(wpc[gi].z, bx.z, acc[gi]);
-            acc[gi] = ft_mfma(wpc[gi].w, bx.w, acc[gi]);
+            acc[gi] = mfma4(wpc[gi].x, bx.x, acc[gi]);
+            acc[gi] = mfma4(wpc[gi].y, bx.y, acc[gi]);
+            acc[gi] = mfma4(wpc[gi].z, bx.z, acc[gi]);
+            acc[gi] = mfma4(wpc[gi].w, bx.w, acc[gi]);
         }
     }
 #endif
@@ -319,11 +282,11 @@ __global__ __launch_bounds__(256, 2) void attention_fwd_tile_kernel(
             val.z = ov.z + acc[gi][2] + bb.z * s; val.w = ov.w + acc[gi][3] + bb.w * s;
             if (rv) *(float4 *)(out + ptl * C + o0 + ol) = val;
             if (stats) {
-                const float s0 = ft_row16_sum(rv ? val.x : 0.f), s1 = ft_row16_sum(rv ? val.y : 0.f);
-                const float s2 = ft_row16_sum(rv ? val.z : 0.f), s3 = ft_row16_sum(rv ? val.w : 0.f);
+                const float s0 = row16_sum(rv ? val.x : 0.f), s1 = row16_sum(rv ? val.y : 0.f);
+                const float s2 = row16_sum(rv ? val.z : 0.f), s3 = row16_sum(rv ? val.w : 0.f);
                 const float d0 = rv ? val.x - s0 * inv : 0.f, d1 = rv ? val.y - s1 * inv : 0.f;
                 const float d2 = rv ? val.z - s2 * inv : 0.f, d3 = rv ? val.w - s3 * inv : 0.f;
-                const float m0 = ft_row16_sum(d0 * d0), m1 = ft_row16_sum(d1 * d1), m2 = ft_row16_sum(d2 * d2), m3 = ft_row16_sum(d3 * d3);
+                const float m0 = row16_sum(d0 * d0), m1 = row16_sum(d1 * d1), m2 = row16_sum(d2 * d2), m3 = row16_sum(d3 * d3);
                 if (l15 == 0) {
                     float *rec = stats + (size_t)tile * 2 * C + o0 + ol;
                     *(float4 *)rec = make_float4(s0, s1, s2, s3);

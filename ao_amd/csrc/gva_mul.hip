@@ -28,41 +28,12 @@
 namespace gva {
 namespace mul {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v4f mfma(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float sum8(float v) {  // all-reduce over the 8 lanes that share lane >> 3
-    v += dpp<0xB1>(v);
-    v += dpp<0x4E>(v);
-    v += dpp<0x141>(v);
-    return v;
-}
-__device__ __forceinline__ float sum_q(float v) {  // all-reduce over the four lane quarters (fixed order)
-    v += __shfl_xor(v, 16, WAVE);
-    v += __shfl_xor(v, 32, WAVE);
-    return v;
-}
-// LDS hand-off inside a wavefront (gva_fwd_tile.hip)
-__device__ __forceinline__ void wave_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__host__ __device__ constexpr int tile_pitch(int C) {  // >= C, = 4 mod 64
-    int p = C;
-    while (p % 64 != 4) p += 4;
-    return p;
-}
-
 constexpr size_t PART_BUDGET = (size_t)16 << 20;  // floats of rows-pass records at most
 constexpr int ROWS_MAX_BLOCKS = 1024;
 
 template <int C>
 struct Cfg {
-    static constexpr int G = C / 8, CT = C / 16, CK = C / 16, GT = (G + 15) / 16, G16 = GT * 16, GP = G + 1, PITCH = tile_pitch(C);
+    static constexpr int G = C / 8, CT = C / 16, CK = C / 16, GT = (G + 15) / 16, G16 = GT * 16, GP = G + 1, PITCH = pitch64(C);
     static constexpr int NW_FWD = C <= 192 ? 4 : 2;              // wavefronts per workgroup: forward and key pass
     static constexpr int NW_ROWS = C <= 192 ? 4 : (C <= 384 ? 2 : 1);  // rows pass (two tiles per wavefront in LDS)
     static constexpr size_t REC = (size_t)C * C + 6 * (size_t)C;  // rows-pass record: g_Wm2 | g_w | g_bm2 | g_a_m xyz | g_b_m
@@ -85,10 +56,10 @@ __device__ __forceinline__ v4f tile_times_rows(const float *tile, const float *_
     auto step = [&](int ck, v4f d) -> v4f {
         const float4 wv = *(const float4 *)(wrow + 16 * ck);
         const float4 av = *(const float4 *)(arow + 16 * ck);
-        d = mfma(av.x, wv.x, d);
-        d = mfma(av.y, wv.y, d);
-        d = mfma(av.z, wv.z, d);
-        d = mfma(av.w, wv.w, d);
+        d = mfma4(av.x, wv.x, d);
+        d = mfma4(av.y, wv.y, d);
+        d = mfma4(av.z, wv.z, d);
+        d = mfma4(av.w, wv.w, d);
         return d;
     };
 #pragma unroll 2
@@ -166,7 +137,7 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_fwd_kernel(long long rows,
         const long long r0 = tile * 16;
         const TileRows T = tile_rows(r0, rows, lk, n, coord, idx, true, l15, q);
         build_pm<C>(sPm, sABm, T.px, T.py, T.pz, l15, q);
-        wave_sync();
+        wave_lds_sync();
 #pragma unroll 1
         for (int ct = 0; ct < K::CT; ++ct) {
             const int c = 16 * ct + l15;
@@ -180,13 +151,13 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_fwd_kernel(long long rows,
             const v4f D = tile_times_rows<C>(sPm, Wm2, ct, l15, q);
             float val[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) val[r] = sum8((kv[r] - qv[r]) * (D[r] + bm) * wc);
+            for (int r = 0; r < 4; ++r) val[r] = row8_sum((kv[r] - qv[r]) * (D[r] + bm) * wc);
             if ((l15 & 7) == 0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sW[(4 * q + r) * GP + 2 * ct + (l15 >> 3)] = val[r];
             }
         }
-        wave_sync();
+        wave_lds_sync();
 #pragma unroll
         for (int t = 0; t < GT; ++t) {
             const int g = 16 * t + l15, gc = g < G ? g : G - 1;
@@ -201,12 +172,12 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_fwd_kernel(long long rows,
                 t2[t] = ok ? __builtin_fmaf(v, v, t2[t]) : t2[t];
             }
         }
-        wave_sync();  // sW and the Pm tile are rewritten by the next trip
+        wave_lds_sync();  // sW and the Pm tile are rewritten by the next trip
     }
 #pragma unroll
     for (int t = 0; t < GT; ++t) {
-        t1[t] = sum_q(t1[t]);
-        t2[t] = sum_q(t2[t]);
+        t1[t] = quarter_sum_shfl(t1[t]);
+        t2[t] = quarter_sum_shfl(t2[t]);
         if (q == 0) { sRed[wid * 2 * G16 + 16 * t + l15] = t1[t]; sRed[wid * 2 * G16 + G16 + 16 * t + l15] = t2[t]; }
     }
     __syncthreads();
@@ -275,7 +246,7 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_rows_kernel(
             sPos[l15] = make_float4(T.px, T.py, T.pz, 0.f);
             build_gwt<C>(sG, sC1, sC2, r0, rows, live, W1, gW1, lane);
             build_pm<C>(sPm, sABm, T.px, T.py, T.pz, l15, q);
-            wave_sync();
+            wave_lds_sync();
             // ---- pem again; g_w, g_bm2, g_query; the g_pem tile
 #pragma unroll 1
             for (int ct = 0; ct < CT; ++ct) {
@@ -299,8 +270,8 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_rows_kernel(
                     gq[r] = u * pem;
                     sGp[(4 * q + r) * PITCH + c] = gp;
                 }
-                aw = sum_q(aw);
-                abm = sum_q(abm);
+                aw = quarter_sum_shfl(aw);
+                abm = quarter_sum_shfl(abm);
                 if (q == 0) { sVec[c] += aw; sVec[C + c] += abm; }
                 // g_query[point] = - sum over the point's k slots (slot 4 q + r of the tile)
                 const float s01 = gq[0] + gq[1], s23 = gq[2] + gq[3];
@@ -314,7 +285,7 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_rows_kernel(
                     s += __shfl_xor(s, 16, WAVE);
                     if (!(q & 1) && T.ok[0]) g_query[T.pt[0] * C + c] = -s;
                 } else {
-                    s = sum_q(s);
+                    s = quarter_sum_shfl(s);
                     if (q == 0) {
                         if (SUB > 1) {
                             const float acc = sub ? sQ[c] + s : s;
@@ -325,7 +296,7 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_rows_kernel(
                     }
                 }
             }
-            wave_sync();
+            wave_lds_sync();
             // ---- g_Pm (slot, c') = sum_ch g_pem[slot][ch] Wm2[ch][c'] -> through the ReLU of Pm -> g_a_m, g_b_m
 #pragma unroll 1
             for (int ctp = 0; ctp < CT; ++ctp) {
@@ -337,10 +308,10 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_rows_kernel(
                     const float4 av = *(const float4 *)(arow + 16 * ck);
                     const float *bp = bcol + (size_t)(16 * ck) * C;
                     const float b0 = bp[0], b1 = bp[C], b2 = bp[2 * C], b3 = bp[3 * C];
-                    d = mfma(av.x, b0, d);
-                    d = mfma(av.y, b1, d);
-                    d = mfma(av.z, b2, d);
-                    d = mfma(av.w, b3, d);
+                    d = mfma4(av.x, b0, d);
+                    d = mfma4(av.y, b1, d);
+                    d = mfma4(av.z, b2, d);
+                    d = mfma4(av.w, b3, d);
                     return d;
                 };
 #pragma unroll 2
@@ -361,7 +332,7 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_rows_kernel(
                     az = __builtin_fmaf(gpre, p4.z, az);
                     ab += gpre;
                 }
-                ax = sum_q(ax); ay = sum_q(ay); az = sum_q(az); ab = sum_q(ab);
+                ax = quarter_sum_shfl(ax); ay = quarter_sum_shfl(ay); az = quarter_sum_shfl(az); ab = quarter_sum_shfl(ab);
                 if (q == 0) { sVec[2 * C + cp] += ax; sVec[3 * C + cp] += ay; sVec[4 * C + cp] += az; sVec[5 * C + cp] += ab; }
             }
             // ---- g_Wm2 (ch, c') += sum over the NW tiles' slots g_pem[slot][ch] Pm[slot][c']: the output tiles dealt to the wavefronts
@@ -377,7 +348,7 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_rows_kernel(
                     const float *tp = wave_base(wv), *tg = tp + 16 * PITCH;
 #pragma unroll
                     for (int st = 0; st < 4; ++st)
-                        acc = mfma(tg[(4 * st + q) * PITCH + 16 * i + l15], tp[(4 * st + q) * PITCH + 16 * j + l15], acc);
+                        acc = mfma4(tg[(4 * st + q) * PITCH + 16 * i + l15], tp[(4 * st + q) * PITCH + 16 * j + l15], acc);
                 }
                 dst[0] = acc[0]; dst[C] = acc[1]; dst[2 * C] = acc[2]; dst[3 * C] = acc[3];
             }
@@ -448,7 +419,7 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_key_kernel(
             const float px = ok ? jx - coord[3 * pp] : 0.f, py = ok ? jy - coord[3 * pp + 1] : 0.f, pz = ok ? jz - coord[3 * pp + 2] : 0.f;
             if (q == 0) sRow[l15] = ok ? (int)r : -1;
             build_pm<C>(sPm, sABm, px, py, pz, l15, q);
-            wave_sync();
+            wave_lds_sync();
             for (int e = lane; e < 16 * G; e += 64) {
                 const int rr = e / G, gg = e - rr * G;
                 const int row = sRow[rr];
@@ -456,7 +427,7 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_key_kernel(
                 const float wv = W1[o], gv = gW1[o];
                 sG[rr * GP + gg] = row >= 0 ? __builtin_fmaf(wv, sC2[gg], gv + sC1[gg]) : 0.f;
             }
-            wave_sync();
+            wave_lds_sync();
 #pragma unroll 1
             for (int ct = 0; ct < K::CT; ++ct) {
                 const int c = 16 * ct + l15;
@@ -465,14 +436,14 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_key_kernel(
                 float s = 0.f;
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) s = __builtin_fmaf(sG[(4 * q + r4) * GP + (c >> 3)] * wc, D[r4] + bm, s);
-                s = sum_q(s);
+                s = quarter_sum_shfl(s);
                 if (q == 0) sK[c] += s;
             }
-            wave_sync();
+            wave_lds_sync();
         }
-        wave_sync();
+        wave_lds_sync();
         for (int c = lane; c < C; c += 64) g_key[j * C + c] = sK[c];
-        wave_sync();
+        wave_lds_sync();
     }
 }
 

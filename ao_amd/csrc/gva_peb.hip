@@ -93,19 +93,6 @@ __global__ __launch_bounds__(TPB) void peb_fwd_kernel(int n, int c, int g, int c
 // A workgroup = one 64-row block x `gpw` groups; with stats != NULL its epilogue leaves the column statistics of `out` for
 // this row block (sum, sum of squares about the block mean: the records of gemm.hip's epilogue, merged by
 // bn_tiles_finalize) -- norm2's statistics pass and its read of `out` disappear.
-typedef float v4f_peb __attribute__((ext_vector_type(4)));
-template <int CTRL>
-__device__ __forceinline__ float peb_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float peb_row16_sum(float v) {  // all-reduce over the 16 lanes that share lane >> 4
-    v += peb_dpp<0xB1>(v);
-    v += peb_dpp<0x4E>(v);
-    v += peb_dpp<0x141>(v);
-    v += peb_dpp<0x140>(v);
-    return v;
-}
-
 template <int C, int PEB_MAX_GPW>  // PEB_MAX_GPW: groups per workgroup (compile-time: per-group registers are arrays of it)
 __global__ __launch_bounds__(TPB) void peb_fwd_mfma_kernel(int n, int g, const float *__restrict__ A,
                                                            const float *__restrict__ Wp2, const float *__restrict__ bp2,
@@ -183,7 +170,7 @@ __global__ __launch_bounds__(TPB) void peb_fwd_mfma_kernel(int n, int g, const f
     }
     __syncthreads();
     float4 val[PEB_MAX_GPW];
-    v4f_peb acc = (v4f_peb){0.f, 0.f, 0.f, 0.f};
+    v4f acc = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int item = 0; item < ITEMS; ++item) {
         constexpr int dummy = 0;
@@ -212,7 +199,7 @@ __global__ __launch_bounds__(TPB) void peb_fwd_mfma_kernel(int n, int g, const f
                 *(float4 *)(out + (size_t)pt * C + col) = v;
             }
             val[gl] = v;
-            acc = (v4f_peb){0.f, 0.f, 0.f, 0.f};
+            acc = (v4f){0.f, 0.f, 0.f, 0.f};
         }
     }
     if (!stats) return;
@@ -223,7 +210,7 @@ __global__ __launch_bounds__(TPB) void peb_fwd_mfma_kernel(int n, int g, const f
 #pragma unroll
     for (int t = 0; t < PEB_MAX_GPW; ++t)
         if (t < ng) {
-            const float sx = peb_row16_sum(val[t].x), sy = peb_row16_sum(val[t].y), sz = peb_row16_sum(val[t].z), s_w = peb_row16_sum(val[t].w);
+            const float sx = row16_sum(val[t].x), sy = row16_sum(val[t].y), sz = row16_sum(val[t].z), s_w = row16_sum(val[t].w);
             if (l15 == 0 && q < 2) *(float4 *)(sS + wid * ncol + t * 8 + 4 * q) = make_float4(sx, sy, sz, s_w);
         }
     __syncthreads();
@@ -252,7 +239,7 @@ __global__ __launch_bounds__(TPB) void peb_fwd_mfma_kernel(int n, int g, const f
             const bool ok = rv && q < 2;
             const float dx = ok ? val[t].x - mean[t].x * inv : 0.f, dy = ok ? val[t].y - mean[t].y * inv : 0.f;
             const float dz = ok ? val[t].z - mean[t].z * inv : 0.f, dw = ok ? val[t].w - mean[t].w * inv : 0.f;
-            const float qx = peb_row16_sum(dx * dx), qy = peb_row16_sum(dy * dy), qz = peb_row16_sum(dz * dz), qw = peb_row16_sum(dw * dw);
+            const float qx = row16_sum(dx * dx), qy = row16_sum(dy * dy), qz = row16_sum(dz * dz), qw = row16_sum(dw * dw);
             if (l15 == 0 && q < 2) *(float4 *)(sS + wid * ncol + t * 8 + 4 * q) = make_float4(qx, qy, qz, qw);
         }
     __syncthreads();

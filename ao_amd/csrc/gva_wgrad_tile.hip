@@ -23,9 +23,6 @@
 
 namespace gva {
 
-typedef float wt_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ wt_v4f wt_mfma(float a, float b, wt_v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 constexpr int WT_PG = 16 * 16 + 4;  // floats per (chunk, group) record of the LDS tile: 16 points x 16 channels (+ 4: quarters on distinct banks)
 
 template <int G, int C, int GB, int NCW>
@@ -59,11 +56,11 @@ __device__ __forceinline__ void wp2_wgrad_tile_body(const dense::WgradJob &J, co
         const int ch = c0 + 16 * ck + l15;
         ab[ck] = make_float4(a[3 * ch], a[3 * ch + 1], a[3 * ch + 2], b[ch]);
     }
-    wt_v4f accW[NGW][NCW];
+    v4f accW[NGW][NCW];
 #pragma unroll
     for (int gi = 0; gi < NGW; ++gi)
 #pragma unroll
-        for (int ck = 0; ck < NCW; ++ck) accW[gi][ck] = (wt_v4f){0.f, 0.f, 0.f, 0.f};
+        for (int ck = 0; ck < NCW; ++ck) accW[gi][ck] = (v4f){0.f, 0.f, 0.f, 0.f};
     float bacc = 0.f;
     const bool bias_thread = cr == 0 && tid < 8 * GB;
     const int bch = bias_thread ? tid : 0;
@@ -107,8 +104,7 @@ __device__ __forceinline__ void wp2_wgrad_tile_body(const dense::WgradJob &J, co
         request(tn, nxt);  // (the last trip repeats its own tile: unconditional loads)
         // ---- relative positions through a wave-private LDS record into the operand layout of phase A (slot 4 st + q)
         sPos[wid * 64 + lane] = cur.pos;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_sync();
         float3 pq[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -120,14 +116,14 @@ __device__ __forceinline__ void wp2_wgrad_tile_body(const dense::WgradJob &J, co
         // ---- phase A: A (group, c') of my points for the NCW chunks -> LDS [chunk][group][point][c']
 #pragma unroll
         for (int ck = 0; ck < NCW; ++ck) {
-            wt_v4f d[4];
+            v4f d[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) d[i] = (wt_v4f){0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < 4; ++i) d[i] = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int st = 0; st < 4; ++st)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    d[i] = wt_mfma(cur.wA[i][st], pe_act(ab[ck].x, ab[ck].y, ab[ck].z, ab[ck].w, pq[i][st].x, pq[i][st].y, pq[i][st].z), d[i]);
+                    d[i] = mfma4(cur.wA[i][st], pe_act(ab[ck].x, ab[ck].y, ab[ck].z, ab[ck].w, pq[i][st].x, pq[i][st].y, pq[i][st].z), d[i]);
             if (q < QB) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -154,7 +150,7 @@ __device__ __forceinline__ void wp2_wgrad_tile_body(const dense::WgradJob &J, co
             for (int ck = 0; ck < NCW; ++ck) {
                 const float *src = sA + (ck * GB + wid + 4 * gi) * PG + q * 16 + l15;
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) accW[gi][ck] = wt_mfma(cur.goA[gi][ks], src[ks * 64], accW[gi][ck]);
+                for (int ks = 0; ks < 4; ++ks) accW[gi][ck] = mfma4(cur.goA[gi][ks], src[ks * 64], accW[gi][ck]);
             }
         __syncthreads();  // the tile is rewritten by the next trip
     }

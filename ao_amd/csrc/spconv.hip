@@ -18,7 +18,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int TM = 64;          // table rows per workgroup
 constexpr int KC = 32;          // input channels per LDS stage
 constexpr int PITCH = KC + 4;   // row r starts in bank 36 r mod 64: 16 rows x 4 columns hit 64 distinct banks
@@ -53,15 +52,15 @@ __global__ __launch_bounds__(256) void conv_kernel(int n_tab, int n_other, int K
         sAny[tid] = any;
     }
     __syncthreads();
-    f32x4 acc[NT];
+    v4f acc[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < NT; ++t) acc[t] = v4f{0.f, 0.f, 0.f, 0.f};
     const int my_row = 16 * w + (lane & 15), quad = lane >> 4;
     for (int kap = 0; kap < K; ++kap) {
         if (!sAny[kap]) continue;  // (the same for every thread of the workgroup)
         if (FORM == SPCONV_SCATTER) {
 #pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < NT; ++t) acc[t] = v4f{0.f, 0.f, 0.f, 0.f};
         }
         for (int c0 = 0; c0 < cin; c0 += KC) {
 #pragma unroll
@@ -171,9 +170,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(int n_tab, int n_other, int 
     const int kap = blockIdx.x / splits, s = blockIdx.x - kap * splits;
     const int co0 = blockIdx.y * 32, ci0 = blockIdx.z * XW;
     const int r_begin = s * rows_per_split, r_end = min(n_tab, r_begin + rows_per_split);
-    f32x4 acc[NJ];
+    v4f acc[NJ];
 #pragma unroll
-    for (int u = 0; u < NJ; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < NJ; ++u) acc[u] = v4f{0.f, 0.f, 0.f, 0.f};
     for (int rb = r_begin; rb < r_end; rb += RC) {
         int j = -1;
         if (tid < RC && rb + tid < r_end) {

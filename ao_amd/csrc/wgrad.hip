@@ -22,7 +22,6 @@ namespace dense {
 // read straight from global memory -- lane l of a fragment holds element [row0 + (l>>4)][col0 + (l&15)],
 // i.e. four 64-byte row segments per load, no LDS staging.  A workgroup = 4 waves = one (up to) 48x48
 // output tile for one chunk of rows; the waves interleave k-steps and are summed through LDS.
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int WG_MT = 3, WG_TILE = 16 * WG_MT, WG_CHUNK = 256, WG_CHUNK_MIN = 128;
 
 // BF16: the U = 8 k-steps of a trip (8 rows per lane and fragment) are exactly the 8-per-lane operand of
@@ -41,13 +40,13 @@ __device__ __forceinline__ void wgrad_direct_tile(const int n, const int cout, c
     const long long r0 = (long long)bx * chunk;
     const long long r1 = (r0 + chunk) < (long long)n ? (r0 + chunk) : (long long)n;
     const int lr = lane >> 4, lc = lane & 15;
-    f32x4 acc[WG_MT][WG_MT];
+    v4f acc[WG_MT][WG_MT];
     float bsum[WG_MT];
 #pragma unroll
     for (int m = 0; m < WG_MT; ++m) {
         bsum[m] = 0.f;
 #pragma unroll
-        for (int t = 0; t < WG_MT; ++t) acc[m][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < WG_MT; ++t) acc[m][t] = (v4f){0.f, 0.f, 0.f, 0.f};
     }
     // (measured and rejected, round 3: columns 3 lc + m per lane so that a lane's three operand values of a k-step are ONE
     // 12-byte load and a row is read as 192 contiguous bytes -- 16 instead of 48 vector-memory instructions per trip: slower at
@@ -193,13 +192,13 @@ __device__ __forceinline__ void wgrad_lds_tile(const int n, const int cout, cons
     const long long r0 = (long long)bx * chunk;
     const long long r1 = (r0 + chunk) < (long long)n ? (r0 + chunk) : (long long)n;
     const int lr = lane >> 4, lc = lane & 15;
-    f32x4 acc[WG_MT][WG_MT];
+    v4f acc[WG_MT][WG_MT];
     float bsum[WG_MT];
 #pragma unroll
     for (int m = 0; m < WG_MT; ++m) {
         bsum[m] = 0.f;
 #pragma unroll
-        for (int t = 0; t < WG_MT; ++t) acc[m][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < WG_MT; ++t) acc[m][t] = (v4f){0.f, 0.f, 0.f, 0.f};
     }
     float xsc_[WG_MT], xsh_[WG_MT];
 #pragma unroll
