@@ -148,6 +148,57 @@ unsigned *ptv2_stream_counters(hipStream_t st) {
     return p;
 }
 
+// --------------------------------------------------------- per-kernel launch limits --
+// What the launchers ask the runtime about a kernel before they launch it, remembered per (kernel, device): the dynamic-LDS
+// limit it has been raised to, and the workgroups of it the device holds at once.  One mutex for both maps: the geometry
+// stream and the helper thread launch beside the training thread.
+namespace {
+std::mutex g_launch_mu;
+struct KernelDev {
+    const void *kernel; int device, threads; size_t lds;   // (threads, lds: 0 in the limit map)
+    bool operator==(const KernelDev &o) const { return kernel == o.kernel && device == o.device && threads == o.threads && lds == o.lds; }
+};
+struct KernelDevHash {
+    size_t operator()(const KernelDev &k) const {
+        return ((std::hash<const void *>()(k.kernel) * 31u + (size_t)k.device) * 31u + (size_t)k.threads) * 31u + k.lds;
+    }
+};
+std::unordered_map<KernelDev, size_t, KernelDevHash> g_lds_limit;   // the largest limit set successfully
+std::unordered_map<KernelDev, int, KernelDevHash> g_resident;
+}  // namespace
+
+int ptv2_kernel_lds(const void *kernel, size_t bytes) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return PTV2_ERR_LAUNCH;
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    const KernelDev key{kernel, device, 0, 0};
+    const auto it = g_lds_limit.find(key);
+    if (it != g_lds_limit.end() && bytes <= it->second) return PTV2_OK;
+    // (the attribute SETS the limit: only a larger request reaches it, so a smaller later one never lowers it)
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return PTV2_ERR_LAUNCH;  // not remembered: the next call asks again
+    }
+    g_lds_limit[key] = bytes;
+    return PTV2_OK;
+}
+
+int ptv2_resident_blocks(const void *kernel, int threads, size_t lds, int occ_fallback, int cu_fallback) {
+    int device = 0, occ = 0, cus = 0;
+    const bool have_device = hipGetDevice(&device) == hipSuccess;
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    const KernelDev key{kernel, device, threads, lds};
+    if (have_device) {
+        const auto it = g_resident.find(key);
+        if (it != g_resident.end()) return it->second;
+    }
+    const bool have_occ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) == hipSuccess && occ >= 1;
+    const bool have_cus = have_device && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus >= 1;
+    const int blocks = (have_occ ? occ : occ_fallback) * (have_cus ? cus : cu_fallback);
+    if (have_occ && have_cus) g_resident[key] = blocks;  // a fall-back is not remembered: the next call asks again
+    return blocks;
+}
+
 // ---------------------------------------------------------------- kernel timer --
 // A debugging / measurement facility, off by default: no events are created and launchers take no extra
 // branch beyond one flag read.  Enabled by bench.py for its roofline object (HIP events on the launch

@@ -22,16 +22,17 @@
 
 static inline int divup(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// Workgroups of `kernel` the current device holds at once: occupancy per compute unit x compute units.  A failing (or
-// non-positive) occupancy query counts as occ_fallback, a failing compute-unit query as cu_fallback (256: the MI355X).  Callers
-// raise the kernel's dynamic-LDS limit first where `lds` needs it, and keep their own cache and clamp: those are tuning
-// decisions (gva_bwd_point.hip: launch_bwd_point).
-static inline int ptv2_resident_blocks(const void *kernel, int threads, size_t lds, int occ_fallback, int cu_fallback = 256) {
-    int occ = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) != hipSuccess || occ < 1) occ = occ_fallback;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = cu_fallback;
-    return occ * cus;
-}
+// The two questions a launcher asks the runtime about a kernel, answered per (kernel, current device) from one table under one
+// mutex (abi.hip), so every site asks on every call and no unit keeps a cache of its own.
+// Every launch with dynamic LDS is preceded by RUN(ptv2_kernel_lds(kern, lds)): the kernel's dynamic-LDS limit on this device is
+// then at least `bytes`.  The runtime is called only when `bytes` exceeds what was set before (a smaller request never lowers
+// the limit); PTV2_ERR_LAUNCH when the runtime refuses or there is no device, and a refusal is not remembered.
+int ptv2_kernel_lds(const void *kernel, size_t bytes);
+// Workgroups of `kernel` the current device holds at once: occupancy per compute unit x compute units, asked once per
+// (kernel, device, threads, lds) -- after ptv2_kernel_lds where `lds` is not 0.  A failing (or non-positive) occupancy query
+// counts as occ_fallback, a failing compute-unit query as cu_fallback (256: the MI355X); such an answer is not remembered.
+// Callers clamp the result: those are tuning decisions (gva_bwd_point.hip: launch_bwd_point).
+int ptv2_resident_blocks(const void *kernel, int threads, size_t lds, int occ_fallback, int cu_fallback = 256);
 
 // Every region of a workspace / saved buffer / arena starts on a 256-byte boundary.
 static constexpr size_t ptv2_align256(size_t v) { return (v + 255) & ~(size_t)255; }

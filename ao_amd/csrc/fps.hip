@@ -356,14 +356,9 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_coop_kernel(const float *__re
 
 // workgroups of the LOCAL kernel the device holds at once (occupancy x compute units), per RC
 int coop_capacity(int RC) {
-    static int cap[4] = {0, 0, 0, 0};
-    const int slot = RC == 2 ? 0 : RC == 4 ? 1 : RC == 8 ? 2 : 3;
-    if (!cap[slot]) {
-        const void *fn = RC == 2 ? (const void *)fps_coop_kernel<2, true> : RC == 4 ? (const void *)fps_coop_kernel<4, true>
-                       : RC == 8 ? (const void *)fps_coop_kernel<8, true> : (const void *)fps_coop_kernel<16, true>;
-        cap[slot] = std::max(1, ptv2_resident_blocks(fn, FPS_THREADS, 0, 1, 0));  // no compute-unit count: capacity 1, not a guess
-    }
-    return cap[slot];
+    const void *fn = RC == 2 ? (const void *)fps_coop_kernel<2, true> : RC == 4 ? (const void *)fps_coop_kernel<4, true>
+                   : RC == 8 ? (const void *)fps_coop_kernel<8, true> : (const void *)fps_coop_kernel<16, true>;
+    return std::max(1, ptv2_resident_blocks(fn, FPS_THREADS, 0, 1, 0));  // no compute-unit count: capacity 1, not a guess
 }
 
 }  // namespace

@@ -621,24 +621,20 @@ __global__ __launch_bounds__(THREADS) void rows_gemm_ksplit_kernel(int m, int n,
 }  // namespace gemm
 
 template <int BN, bool KM, int K>
-static void launch_direct(dim3 grid, hipStream_t st, int m, int n, const float *X, const float *W, const float *bias, float *Y,
-                          int accumulate, int ncb, const gemm::GemmMulti &gm) {
+static int launch_direct(dim3 grid, hipStream_t st, int m, int n, const float *X, const float *W, const float *bias, float *Y,
+                         int accumulate, int ncb, const gemm::GemmMulti &gm) {
     const size_t lds = sizeof(float) * ((size_t)BN * (K + 8) + 2 * K);
-    if (ptv2_matmul_bf16()) {
-        auto kern = gemm::rows_gemm_direct_kernel<BN, KM, K, true>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(gemm::THREADS), lds, st, m, n, X, W, bias, Y, accumulate, ncb, gm);
-    } else {
-        auto kern = gemm::rows_gemm_direct_kernel<BN, KM, K, false>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(gemm::THREADS), lds, st, m, n, X, W, bias, Y, accumulate, ncb, gm);
-    }
+    auto kern = ptv2_matmul_bf16() ? gemm::rows_gemm_direct_kernel<BN, KM, K, true> : gemm::rows_gemm_direct_kernel<BN, KM, K, false>;
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
+    hipLaunchKernelGGL(kern, grid, dim3(gemm::THREADS), lds, st, m, n, X, W, bias, Y, accumulate, ncb, gm);
+    return PTV2_OK;
 }
 
 // the direct form exists for BN = 16 / 48 and K = 48 / 96 / 192 / 384 (every Linear of the S3DIS / ScanNet configurations
 // except the 512-wide ScanNet level); AO_AMD_GEMM=lds selects the LDS-staged kernel (A/B switch of the tests)
+// (false: not this form; true: launched, or refused with *rc)
 static bool launch_gemm_direct(int bn, bool kmajor, dim3 grid, hipStream_t st, int m, int n, int k, const float *X, const float *W,
-                               const float *bias, float *Y, int accumulate, int ncb, const gemm::GemmMulti &gm) {
+                               const float *bias, float *Y, int accumulate, int ncb, const gemm::GemmMulti &gm, int *rc) {
     const char *e = getenv("AO_AMD_GEMM");
     if ((e && e[0] == 'l') || (bn != 16 && bn != 48) || (k != 48 && k != 96 && k != 192 && k != 384)) return false;
     // Where it pays (per (kernel, grid) durations of one step, profiles/r03_*): k = 48 -- the full-resolution level, thousands
@@ -648,7 +644,7 @@ static bool launch_gemm_direct(int bn, bool kmajor, dim3 grid, hipStream_t st, i
     // the chunked loop's prefetch under the MFMAs wins (14.7 vs 20.2 us for the 3-pair input gradient at 4.5 k x 192):
     // those stay on the LDS-staged kernel.  AO_AMD_GEMM=direct forces the direct form wherever it exists (tests).
     if (!(e && e[0] == 'd') && !(k == 48 || (!kmajor && bn == 48 && k <= 192))) return false;
-#define GD(BN, KM, KK) launch_direct<BN, KM, KK>(grid, st, m, n, X, W, bias, Y, accumulate, ncb, gm)
+#define GD(BN, KM, KK) *rc = launch_direct<BN, KM, KK>(grid, st, m, n, X, W, bias, Y, accumulate, ncb, gm)
 #define GDK(BN, KM)                                                                   \
     switch (k) { case 48: GD(BN, KM, 48); break; case 96: GD(BN, KM, 96); break; case 192: GD(BN, KM, 192); break; default: GD(BN, KM, 384); break; }
     if (bn == 16) { if (kmajor) { GDK(16, true) } else { GDK(16, false) } }
@@ -734,9 +730,10 @@ static bool try_ksplit(int m, int n, int k, bool kmajor, int products, hipStream
     return true;
 }
 
-static void launch_gemm(int bn, bool kmajor, bool wide_k, dim3 grid, hipStream_t st, int m, int n, int k, const float *X,
-                        const float *W, const float *bias, float *Y, int accumulate, int ncb, const gemm::GemmMulti &gm) {
-    if (launch_gemm_direct(bn, kmajor, grid, st, m, n, k, X, W, bias, Y, accumulate, ncb, gm)) return;
+static int launch_gemm(int bn, bool kmajor, bool wide_k, dim3 grid, hipStream_t st, int m, int n, int k, const float *X,
+                       const float *W, const float *bias, float *Y, int accumulate, int ncb, const gemm::GemmMulti &gm) {
+    int rc = PTV2_OK;
+    if (launch_gemm_direct(bn, kmajor, grid, st, m, n, k, X, W, bias, Y, accumulate, ncb, gm, &rc)) return rc;
 #define GO(BN, KM, KC) launch_one<BN, KM, KC>(grid, st, m, n, k, X, W, bias, Y, accumulate, ncb, gm)
     if (bn == 16) {
         if (kmajor) { if (wide_k) GO(16, true, 64); else GO(16, true, 32); }
@@ -752,6 +749,7 @@ static void launch_gemm(int bn, bool kmajor, bool wide_k, dim3 grid, hipStream_t
         else { if (wide_k) GO(64, false, 64); else GO(64, false, 32); }
     }
 #undef GO
+    return PTV2_OK;
 }
 
 // Y (m,n) [+]= X (m,k) op(W) + bias.  w_kmajor == 0: W is (n,k) row-major (y = x W^T, nn.Linear forward);
@@ -772,7 +770,7 @@ extern "C" int rows_gemm_hip_launcher(int m, int n, int k, const float *X, const
         PtvScopedTimer t(KID_ROWS_GEMM + (n48 ? 0 : 4) + (w_kmajor ? 2 : 0) + (k >= 192 ? 1 : 0), st,
                          4.0 * ((double)m * (n + k) + (double)n * k));
         if (!try_ksplit(m, n, k, w_kmajor != 0, 1, st, X, W, bias, Y, accumulate, GemmMulti{}, false))
-            launch_gemm(bn, w_kmajor != 0, k >= 192, grid, st, m, n, k, X, W, bias, Y, accumulate, ncb, GemmMulti{});
+            RUN(launch_gemm(bn, w_kmajor != 0, k >= 192, grid, st, m, n, k, X, W, bias, Y, accumulate, ncb, GemmMulti{}));
     }
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
@@ -815,7 +813,7 @@ extern "C" int rows_gemm_fused_hip_launcher(int m, int n, int k, int count, int 
         bool records = false;
         for (int i = 0; i < count; ++i) records = records || gm.stats[i] != nullptr;
         if (!try_ksplit(m, n, k, w_kmajor != 0, sum ? 1 : count, st, gm.X[0], gm.W[0], b0, gm.Y[0], accumulate, gm, records))
-            launch_gemm(bn, w_kmajor != 0, k >= 192, grid, st, m, n, k, gm.X[0], gm.W[0], b0, gm.Y[0], accumulate, ncb, gm);
+            RUN(launch_gemm(bn, w_kmajor != 0, k >= 192, grid, st, m, n, k, gm.X[0], gm.W[0], b0, gm.Y[0], accumulate, ncb, gm));
     }
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
@@ -858,7 +856,7 @@ extern "C" int rows_gemm_bnbwd_hip_launcher(int m, int n, int k, int count, cons
         PtvScopedTimer t(KID_ROWS_GEMM + (n48 ? 0 : 4) + (w_kmajor ? 2 : 0) + (k >= 192 ? 1 : 0), st,
                          4.0 * ((double)m * (2 * n + count * k) + (double)count * n * k));
         if (!try_ksplit(m, n, k, w_kmajor != 0, 1, st, gm.X[0], gm.W[0], nullptr, Y, 0, gm, true))
-            launch_gemm(bn, w_kmajor != 0, k >= 192, grid, st, m, n, k, gm.X[0], gm.W[0], nullptr, Y, 0, ncb, gm);
+            RUN(launch_gemm(bn, w_kmajor != 0, k >= 192, grid, st, m, n, k, gm.X[0], gm.W[0], nullptr, Y, 0, ncb, gm));
     }
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;

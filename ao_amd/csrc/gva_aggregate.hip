@@ -551,6 +551,7 @@ int gva_aggregate_forward(const GvaPlan &P, int n, int k, int c, int g, const At
         // w + idx + coord in; v rows (each unique row once); out_v and A out
         PtvScopedTimer t(KID_AGG_TILE, st, 4.0 * ((double)rows * (g + 1) + (double)n * (3 + 2 * c) + (double)n * g * c));
 #define CALL(GG)                                                                                                       \
+    RUN(ptv2_kernel_lds((const void *)aggregate_tile_kernel<GG>, lds));                                                \
     hipLaunchKernelGGL(aggregate_tile_kernel<GG>, dim3((n + tp - 1) / tp), dim3(TPB), lds, st, n, k, c, tp, (const float *)O.w, \
                        I.v, I.a, I.b, I.coord, I.idx, O.out_v, O.A)
         GVA_DISPATCH_G(g, CALL)
@@ -626,9 +627,7 @@ int gva_aggregate_backward(const GvaPlan &P, int n, int k, int c, int g, const A
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / lds_tile));
     const int nb_tile = std::min(n, std::min(256 * per_cu, (int)BWD_TILE_BLOCKS));
 #define CALL(GG)                                                                                                        \
-    if (lds_tile > 32 * 1024)                                                                                           \
-        (void)hipFuncSetAttribute((const void *)aggregate_bwd_tile_kernel<GG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)lds_tile);                                                                       \
+    RUN(ptv2_kernel_lds((const void *)aggregate_bwd_tile_kernel<GG>, lds_tile));                                        \
     hipLaunchKernelGGL(aggregate_bwd_tile_kernel<GG>, dim3(nb_tile), dim3(WAVE), lds_tile, st, n, k, c, X.w, I.v, I.a, I.b, I.coord, \
                        I.idx, X.g_out, X.g_A, X.g_sw, gw, X.inv_ptr ? (float *)nullptr : O.gv, part)
     {

@@ -327,9 +327,7 @@ int gva_logits_backward_foldw(const GvaPlan &P, int n, int k, int c, int g, cons
     }
     const int nb_par = stage_grid(rows, PR_TILE, par_cap);
 #define CALL(GG)                                                                                                   \
-    if (comb_bytes > 32 * 1024)                                                                                    \
-        (void)hipFuncSetAttribute((const void *)logits_bwd_params_kernel<GG>,                                      \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)comb_bytes);                    \
+    RUN(ptv2_kernel_lds((const void *)logits_bwd_params_kernel<GG>, comb_bytes));                                  \
     hipLaunchKernelGGL(logits_bwd_params_kernel<GG>, dim3(nb_par), dim3(TPB), comb_bytes, st, n, k, c, I.a, I.b, I.M, I.coord, \
                        I.idx, (const float *)gWt, ppart)
     {

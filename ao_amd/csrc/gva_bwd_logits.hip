@@ -299,11 +299,8 @@ int launch_logits_bwd_fused(int n, int k, const LogitsIn &I, const LogitsBwdIn &
     const size_t lds = sizeof(float4) * (C + 4 * 2 * 16) + sizeof(float) * (2 * K::GT * 16 + (K::PW > 1 ? K::REC : 0));
     auto kern = logits_bwd_fused_kernel<G, C, NW>;
     // exactly the co-resident workgroups (every one stages its constants once, then walks its points; as gva_bwd_point)
-    static int resident = 0;
-    if (!resident) {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 512));
-    }
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
+    const int resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 512));
     const long long groups = ((long long)n + K::PW - 1) / K::PW;
     long long cap = std::min<long long>(resident, (long long)(part_floats_avail / K::REC));
     if (cap < 1) return PTV2_ERR_WORKSPACE;
@@ -506,10 +503,9 @@ int launch_logits_bwd_fused6(int n, const LogitsIn &I, const LogitsBwdIn &X, con
     constexpr int REC = C * 10 + 16;
     const size_t lds = sizeof(float4) * (C + 4 * 2 * 16) + sizeof(float) * (2 * 16 + 4 * 96 + REC);
     auto kern = logits_bwd_fused6_kernel<C>;
-    static int resident = 0;  // exactly the co-resident workgroups, as launch_logits_bwd_fused
-    if (!resident) {
-        resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 1024));
-    }
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
+    // exactly the co-resident workgroups, as launch_logits_bwd_fused
+    const int resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 1024));
     const long long groups = ((long long)n + 3) / 4;
     long long cap = std::min<long long>(resident, (long long)(part_floats_avail / REC));
     if (cap < 1) return PTV2_ERR_WORKSPACE;
@@ -728,11 +724,8 @@ int launch_logits_fwd_mfma(int n, int k, const LogitsIn &I, const LogitsOut &O, 
     const size_t lds = sizeof(float4) * (C + 4 * 2 * 16) + sizeof(int) * 4 * 2 * 16 +
                        (NW > 1 ? sizeof(float) * (size_t)PW * NW * GT * 4 * 64 : 0);
     auto kern = logits_fwd_mfma_kernel<G, C, NW>;
-    static int resident = 0;
-    if (!resident) {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), MAX_BLOCKS));
-    }
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
+    const int resident = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), MAX_BLOCKS));
     const long long groups = ((long long)n + PW - 1) / PW;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(groups, resident));
     const bool own_final = (size_t)nblk * 2 * G <= FUSED_FINAL_MAX;

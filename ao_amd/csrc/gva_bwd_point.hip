@@ -1074,7 +1074,7 @@ int launch_params_point(int n, int k, const LogitsIn &I, const float *gWt, float
     const long long groups = ((long long)n + PW - 1) / PW;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(groups, max_blocks));
     auto kern = logits_params_point_kernel<G, C, NW>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, k, I.a, I.b, I.M, I.coord, I.idx, gWt, part);
     *nblk_out = nblk;
     return PTV2_OK;
@@ -1095,13 +1095,8 @@ int launch_bwd_point(int n, int k, const AttnIn &I, const AttnBwdIn &X, const At
     const bool dropping = drop.thresh != 0;
     auto kern = (HAS_LOCAL && local) ? (dropping ? attention_bwd_point_kernel<G, C, NW, HAS_LOCAL, true> : attention_bwd_point_kernel<G, C, NW, HAS_LOCAL, false>)
                                      : (dropping ? attention_bwd_point_kernel<G, C, NW, false, true> : attention_bwd_point_kernel<G, C, NW, false, false>);
-    static int resident_of[2][2] = {{0, 0}, {0, 0}};
-    int *resident = resident_of[dropping];
-    if (!resident[local]) {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        resident[local] = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 512));
-    }
-    const long long cap = resident[local];
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
+    const long long cap = std::max(64, std::min(ptv2_resident_blocks((const void *)kern, 256, lds, 1), 512));
     const long long groups = ((long long)n + K::PW - 1) / K::PW;
     const int nblk = (int)std::max<long long>(1, std::min<long long>(groups, cap));
     const size_t dump_at = ((size_t)nblk * K::PF + 3) & ~(size_t)3;  // 16 dump rows of G16 floats behind the records

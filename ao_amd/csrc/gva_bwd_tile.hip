@@ -513,11 +513,7 @@ static int launch_bwd_tile_mixed(int n, int nfull, const AttnIn &I, const AttnBw
     const size_t lds = sizeof(float) * std::max(K8::lds_floats, K4::lds_floats);
     const bool dropping = drop.thresh != 0;
     auto kern = dropping ? attention_bwd_tile_mixed_kernel<G, C, true> : attention_bwd_tile_mixed_kernel<G, C, false>;
-    static bool configured[2] = {false, false};
-    if (!configured[dropping]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PTV2_ERR_LAUNCH;
-        configured[dropping] = true;
-    }
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
     const int ntail = (int)((n - (long long)nfull * 8 + 3) / 4);
     const int nblk = nfull + ntail;
     if ((size_t)nblk * K8::PF > part_floats_avail) return PTV2_ERR_WORKSPACE;
@@ -526,17 +522,16 @@ static int launch_bwd_tile_mixed(int n, int nfull, const AttnIn &I, const AttnBw
     launch_finalize(st, (const float *)part, nblk, K8::PF, MapBwdPoint{O.ga, O.gb, O.gsc, O.gsh, O.gWw2, O.gbw2, C, G});
     return PTV2_OK;
 }
-// whole rounds of resident workgroups the 8-point tiles fill, when what is left is at most half a round (else 0: plain launch)
+// whole rounds of resident workgroups the 8-point tiles fill, when what is left is at most half a round (else 0: plain launch).
+// A count, not a status: a refused LDS raise also gives 0, and the plain launch then reports its own kernel's raise.
 template <int G, int C>
 static int bwd_tile_full_rounds(int n) {
-    static int slots = 0;
-    if (!slots) {
-        using K8 = BwdTileCfg<G, C, 8>;
-        using K4 = BwdTileCfg<G, C, 4>;
-        const size_t lds = sizeof(float) * std::max(K8::lds_floats, K4::lds_floats);
-        (void)hipFuncSetAttribute((const void *)attention_bwd_tile_mixed_kernel<G, C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        slots = ptv2_resident_blocks((const void *)attention_bwd_tile_mixed_kernel<G, C, false>, 256, lds, 2);
-    }
+    using K8 = BwdTileCfg<G, C, 8>;
+    using K4 = BwdTileCfg<G, C, 4>;
+    const size_t lds = sizeof(float) * std::max(K8::lds_floats, K4::lds_floats);
+    const void *kern = (const void *)attention_bwd_tile_mixed_kernel<G, C, false>;  // (the non-dropping instance is asked, whichever runs)
+    if (ptv2_kernel_lds(kern, lds) != PTV2_OK) return 0;
+    const int slots = ptv2_resident_blocks(kern, 256, lds, 2);
     static const bool off = ptv2_env_is("AO_AMD_BT_MIXED", '0');
     const int nt8 = (n + 7) / 8, full = nt8 / slots * slots, tail = nt8 - full;
     return (!off && full > 0 && tail > 0 && 2 * tail <= slots) ? full : 0;
@@ -549,11 +544,7 @@ static int launch_bwd_tile(int n, const AttnIn &I, const AttnBwdIn &X, const Att
     const size_t lds = sizeof(float) * K::lds_floats;
     const bool dropping = drop.thresh != 0;
     auto kern = dropping ? attention_bwd_tile_kernel<G, C, TP, true> : attention_bwd_tile_kernel<G, C, TP, false>;
-    static bool configured[2] = {false, false};
-    if (!configured[dropping]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PTV2_ERR_LAUNCH;
-        configured[dropping] = true;
-    }
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
     const int nblk = (n + TP - 1) / TP;
     if ((size_t)nblk * K::PF > part_floats_avail) return PTV2_ERR_WORKSPACE;
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, n, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.v, I.a, I.b, I.coord, I.idx, X.g_out,

@@ -306,15 +306,11 @@ int gva_logits_forward_fold(const GvaPlan &P, int n, int k, int c, int g, const 
     if (own_final && !cnt) return PTV2_ERR_LAUNCH;
 #define CALL(GG)                                                                                                   \
     if (split) {                                                                                                   \
-        if (lds > 32 * 1024)                                                                                       \
-            (void)hipFuncSetAttribute((const void *)logits_fwd_kernel<GG, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)lds);                                                                   \
+        RUN(ptv2_kernel_lds((const void *)logits_fwd_kernel<GG, 4>, lds));                                         \
         hipLaunchKernelGGL((logits_fwd_kernel<GG, 4>), dim3(nblk), dim3(TPB), lds, st, n, k, c, I.kW, I.qW, I.a, I.b, I.M, I.cW, \
                            I.coord, I.idx, O.W1, part, cnt ? cnt + CNT_LOGITS_FWD : nullptr, O.T1, O.T2, F);                       \
     } else {                                                                                                       \
-        if (lds > 32 * 1024)                                                                                       \
-            (void)hipFuncSetAttribute((const void *)logits_fwd_kernel<GG, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)lds);                                                                   \
+        RUN(ptv2_kernel_lds((const void *)logits_fwd_kernel<GG, 1>, lds));                                         \
         hipLaunchKernelGGL((logits_fwd_kernel<GG, 1>), dim3(nblk), dim3(TPB), lds, st, n, k, c, I.kW, I.qW, I.a, I.b, I.M, I.cW, \
                            I.coord, I.idx, O.W1, part, cnt ? cnt + CNT_LOGITS_FWD : nullptr, O.T1, O.T2, F);                       \
     }

@@ -314,8 +314,7 @@ int gva_fwd_point_launch(int n, int k, int c, int g, const gva::AttnIn &I, const
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (n + 63) / 64;
     // every workgroup the same number of 64-row blocks, and all of them resident at once
-    static int resident = 0;
-    if (!resident) resident = std::max(64, ptv2_resident_blocks((const void *)attention_fwd_point6_kernel<true>, 256, 0, 1));
+    const int resident = std::max(64, ptv2_resident_blocks((const void *)attention_fwd_point6_kernel<true>, 256, 0, 1));
     const int rounds = (nblk + resident - 1) / resident;
     const int grid = (nblk + rounds - 1) / rounds;
     // W1 + idx + coord + v rows (each unique row once) in; w, sw, A, out out

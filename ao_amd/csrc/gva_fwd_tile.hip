@@ -304,11 +304,7 @@ static int launch_fwd_tile(int n, const AttnIn &I, const AttnFwdOut &O, PtvDrop 
     const bool dropping = drop.thresh != 0;
     auto kern = O.A ? (dropping ? attention_fwd_tile_kernel<G, C, GB, true, true> : attention_fwd_tile_kernel<G, C, GB, true, false>)
                       : (dropping ? attention_fwd_tile_kernel<G, C, GB, false, true> : attention_fwd_tile_kernel<G, C, GB, false, false>);
-    static bool configured[2][2] = {{false, false}, {false, false}};
-    if (!configured[O.A != nullptr][dropping]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PTV2_ERR_LAUNCH;
-        configured[O.A != nullptr][dropping] = true;
-    }
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
     hipLaunchKernelGGL(kern, dim3((n + 15) / 16, G / GB), dim3(256), lds, st, n, I.W1, I.sc, I.sh, I.Ww2, I.bw2, I.v, I.a, I.b, I.coord,
                        I.idx, I.Wp2, I.bp2, O.w, O.sw, O.out, O.stats, O.A, drop);
     return PTV2_OK;

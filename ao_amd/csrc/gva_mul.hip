@@ -447,11 +447,6 @@ __global__ __launch_bounds__(64 * NW) void mul_logits_bwd_key_kernel(
     }
 }
 
-template <class Kern>
-static int set_lds(Kern kern, size_t lds) {
-    return hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? PTV2_OK : PTV2_ERR_LAUNCH;
-}
-
 template <int C>
 static int launch_fwd(int n, int k, int lk, const float *key, const float *query, const float *w, const float *a_m, const float *b_m,
                       const float *Wm2, const float *bm2, const float *coord, const int *idx, float *W1, double *T1, double *T2,
@@ -460,8 +455,7 @@ static int launch_fwd(int n, int k, int lk, const float *key, const float *query
     constexpr int NW = K::NW_FWD;
     const size_t lds = sizeof(float) * (K::shared_floats + (size_t)NW * 2 * K::G16 + (size_t)NW * K::fwd_wave_floats);
     auto kern = mul_logits_fwd_kernel<C, NW>;
-    static bool configured = false;
-    if (!configured) { RUN(set_lds(kern, lds)); configured = true; }
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
     const long long rows = (long long)n * k, ntiles = (rows + 15) / 16;
     const int nblk = (int)std::max<long long>(1, std::min<long long>((ntiles + NW - 1) / NW, MAX_BLOCKS));
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * NW), lds, st, rows, lk, n, key, query, w, a_m, b_m, Wm2, bm2, coord, idx, W1, part);
@@ -480,8 +474,7 @@ static int launch_bwd(int n, int k, int lk, const float *key, const float *query
         constexpr int NW = K::NW_ROWS;
         const size_t lds = sizeof(float) * (K::shared_floats + (size_t)NW * K::rows_wave_floats);
         auto kern = mul_logits_bwd_rows_kernel<C, NW>;
-        static bool configured = false;
-        if (!configured) { RUN(set_lds(kern, lds)); configured = true; }
+        RUN(ptv2_kernel_lds((const void *)kern, lds));
         const int sub = k > 16 ? k / 16 : 1;
         const long long units = (ntiles + sub - 1) / sub;
         const int nblk = (int)std::max<long long>(1, std::min<long long>((units + NW - 1) / NW, rows_blocks_cap(K::REC)));
@@ -493,8 +486,7 @@ static int launch_bwd(int n, int k, int lk, const float *key, const float *query
         constexpr int NW = K::NW_FWD;
         const size_t lds = sizeof(float) * (K::shared_floats + (size_t)NW * K::key_wave_floats);
         auto kern = mul_logits_bwd_key_kernel<C, NW>;
-        static bool configured = false;
-        if (!configured) { RUN(set_lds(kern, lds)); configured = true; }
+        RUN(ptv2_kernel_lds((const void *)kern, lds));
         const int nblk = (int)std::max<long long>(1, std::min<long long>(((long long)n + NW - 1) / NW, MAX_BLOCKS));
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * NW), lds, st, rows, lk, n, w, a_m, b_m, Wm2, bm2, coord, W1, gW1, gT1, gT2, inv_ptr,
                            inv_rows, g_key);

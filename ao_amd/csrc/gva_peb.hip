@@ -359,17 +359,18 @@ extern "C" int gva_peb_forward_hip_launcher(int n, int c, int g, const float *A,
 }
 
 template <int C, int GPW>
-static void launch_peb_mfma_g(int n, int g, const AttnIn &I, const AttnFwdOut &O, hipStream_t st) {
+static int launch_peb_mfma_g(int n, int g, const AttnIn &I, const AttnFwdOut &O, hipStream_t st) {
     const int nrb = (n + 63) / 64;
     const size_t lds = sizeof(float) * ((size_t)GPW * 8 * (C + 8) + 4 * GPW * 8);
     auto kern = peb_fwd_mfma_kernel<C, GPW>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    RUN(ptv2_kernel_lds((const void *)kern, lds));
     hipLaunchKernelGGL(kern, dim3(nrb, (g + GPW - 1) / GPW), dim3(TPB), lds, st, n, g, (const float *)O.A, I.Wp2, I.bp2,
                        (const float *)O.sw, (const float *)O.out_v, O.out, O.stats);
+    return PTV2_OK;
 }
 
 template <int C>
-static void launch_peb_mfma(int n, int g, const AttnIn &I, const AttnFwdOut &O, hipStream_t st) {
+static int launch_peb_mfma(int n, int g, const AttnIn &I, const AttnFwdOut &O, hipStream_t st) {
     const int nrb = (n + 63) / 64;
     // groups per workgroup: as many (of 6, 3, 2, 1) as keep >= ~512 workgroups in the launch (each stages its Wp2 rows once)
     const int opts[4] = {6, 3, 2, 1};
@@ -377,10 +378,10 @@ static void launch_peb_mfma(int n, int g, const AttnIn &I, const AttnFwdOut &O, 
     for (int i = 0; i < 4; ++i)
         if ((long long)nrb * ((g + opts[i] - 1) / opts[i]) >= 512 || opts[i] == 1) { gpw = opts[i]; break; }
     switch (gpw) {
-        case 6: launch_peb_mfma_g<C, 6>(n, g, I, O, st); break;
-        case 3: launch_peb_mfma_g<C, 3>(n, g, I, O, st); break;
-        case 2: launch_peb_mfma_g<C, 2>(n, g, I, O, st); break;
-        default: launch_peb_mfma_g<C, 1>(n, g, I, O, st); break;
+        case 6: return launch_peb_mfma_g<C, 6>(n, g, I, O, st);
+        case 3: return launch_peb_mfma_g<C, 3>(n, g, I, O, st);
+        case 2: return launch_peb_mfma_g<C, 2>(n, g, I, O, st);
+        default: return launch_peb_mfma_g<C, 1>(n, g, I, O, st);
     }
 }
 
@@ -394,11 +395,11 @@ int gva_peb_forward_stats(int n, int c, int g, const AttnIn &I, const AttnFwdOut
         hipStream_t st = (hipStream_t)stream;
         PtvScopedTimer t(KID_PEB_FWD, st, 4.0 * ((double)n * g * c + 2.0 * n * c + (double)n * g + (double)c * c));
         switch (c) {
-            case 48: launch_peb_mfma<48>(n, g, I, O, st); break;
-            case 96: launch_peb_mfma<96>(n, g, I, O, st); break;
-            case 192: launch_peb_mfma<192>(n, g, I, O, st); break;
-            case 384: launch_peb_mfma<384>(n, g, I, O, st); break;
-            default: launch_peb_mfma<512>(n, g, I, O, st); break;
+            case 48: RUN(launch_peb_mfma<48>(n, g, I, O, st)); break;
+            case 96: RUN(launch_peb_mfma<96>(n, g, I, O, st)); break;
+            case 192: RUN(launch_peb_mfma<192>(n, g, I, O, st)); break;
+            case 384: RUN(launch_peb_mfma<384>(n, g, I, O, st)); break;
+            default: RUN(launch_peb_mfma<512>(n, g, I, O, st)); break;
         }
         if (O.stats && stats_done) *stats_done = 64;
         PTV2_CHECK_LAUNCH();
@@ -419,8 +420,7 @@ int gva_peb_forward_stats(int n, int c, int g, const AttnIn &I, const AttnFwdOut
     const long long slots = 256LL * std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1));
     const long long cap = std::min<long long>(lds > 40 * 1024 ? 256 : 1024, std::max<long long>(1, slots / ny));
     const int gx = (int)std::min<long long>(((long long)n + tp - 1) / tp, cap);
-    if (lds > 32 * 1024)
-        (void)hipFuncSetAttribute((const void *)peb_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    RUN(ptv2_kernel_lds((const void *)peb_fwd_kernel, lds));
     {
         PtvScopedTimer t(KID_PEB_FWD, (hipStream_t)stream, 4.0 * ((double)n * g * c + 2.0 * n * c + (double)n * g + (double)c * c));
         hipLaunchKernelGGL(peb_fwd_kernel, dim3(gx, ny), dim3(TPB), lds, (hipStream_t)stream, n, c, g, ct, (const float *)O.A, I.Wp2,

@@ -239,23 +239,15 @@ size_t gva_wgrad_tile_plan(dense::WgradJob *J, int max_splits) {
     return (size_t)J->chunks * J->rec;
 }
 
-static bool wgrad_tile_configure() {
-    static const bool ok = hipFuncSetAttribute((const void *)gva::wp2_wgrad_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)gva::WT_LDS_BYTES) == hipSuccess &&
-                           hipFuncSetAttribute((const void *)gva::wp2_wgrad_tile_kernel_jobs, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)gva::WT_LDS_BYTES) == hipSuccess;
-    return ok;
-}
-
 int gva_wgrad_tile_launch_one(const dense::WgradJob &J, hipStream_t st) {
-    if (!wgrad_tile_configure()) return PTV2_ERR_LAUNCH;
+    RUN(ptv2_kernel_lds((const void *)gva::wp2_wgrad_tile_kernel, gva::WT_LDS_BYTES));
     hipLaunchKernelGGL(gva::wp2_wgrad_tile_kernel, dim3((unsigned)J.wgs), dim3(256), gva::WT_LDS_BYTES, st, J);
     return PTV2_OK;
 }
 
 // pos_wgs > 0: every job carries a posrel buffer (J.mX[0]) and its first workgroup of the position launch (J.ldy)
 int gva_wgrad_tile_launch_jobs(const dense::WgradJob *table, int njobs, int wgs, int pos_wgs, hipStream_t st) {
-    if (!wgrad_tile_configure()) return PTV2_ERR_LAUNCH;
+    RUN(ptv2_kernel_lds((const void *)gva::wp2_wgrad_tile_kernel_jobs, gva::WT_LDS_BYTES));
     if (pos_wgs > 0) hipLaunchKernelGGL(gva::wp2_posrel_kernel_jobs, dim3((unsigned)pos_wgs), dim3(256), 0, st, table, njobs);
     hipLaunchKernelGGL(gva::wp2_wgrad_tile_kernel_jobs, dim3((unsigned)wgs), dim3(256), gva::WT_LDS_BYTES, st, table, njobs);
     return PTV2_OK;

@@ -314,11 +314,7 @@ extern "C" int inverse_tables_hip_launcher(int count, const ptv2_inverse_job *jo
     int2 *pairs = (int2 *)p;                                   p += P.pair_bytes;
     int *spill = (int *)p;
     const size_t lds = build_lds_bytes(P.max_width);
-    static bool raised = [] {
-        return hipFuncSetAttribute((const void *)inv_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)build_lds_bytes(MAX_WIDTH)) == hipSuccess;
-    }();
-    if (!raised) return PTV2_ERR_LAUNCH;
+    RUN(ptv2_kernel_lds((const void *)inv_build_kernel, build_lds_bytes(MAX_WIDTH)));
     const dim3 chunks((unsigned)P.total_chunks);
     hipLaunchKernelGGL(inv_split_kernel<false>, chunks, dim3(TPB), 0, st, P.J, cells, pairs, handoff, P.scan_wgs, P.cells_used,
                        P.cells_padded);

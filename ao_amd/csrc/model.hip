@@ -398,6 +398,7 @@ int linbn_forward(const ptv2_model *M, const ptv2_linbn &L, const LinBnSaved &S,
         RUN(rows_gemm_hip_launcher(n, L.cout, L.cin, x, L.w, 0, L.b, S.h, 0, stream));
     } else {
         const size_t lds = sizeof(float) * ((size_t)L.cout * (L.cin | 1) + L.cout);
+        RUN(ptv2_kernel_lds((const void *)small_linear_fwd_kernel, lds));
         hipLaunchKernelGGL(small_linear_fwd_kernel, dim3(grid_for((long long)n * L.cout)), dim3(TPB), lds, st, (long long)n, L.cin,
                            L.cout, x, L.w, L.b, S.h);
     }
@@ -639,15 +640,19 @@ int model_forward(const ptv2_model *M, void *workspace, size_t workspace_bytes, 
         const int c0 = M->head.cout, nc = M->num_classes;
         const size_t lds = sizeof(float) * ((size_t)nc * (c0 | 1) + nc);  // (covers small_linear_fwd's odd row pitch)
         const int gr = grid_for(M->level[0].n);
-        if (c0 % 4 == 0 && nc == 13)
+        if (c0 % 4 == 0 && nc == 13) {
+            RUN(ptv2_kernel_lds((const void *)classifier_fwd_kernel<13>, lds));
             hipLaunchKernelGGL(classifier_fwd_kernel<13>, dim3(gr), dim3(TPB), lds, st, (long long)M->level[0].n, c0,
                                (const float *)A.head.y, M->head_w, M->head_b, M->logits);
-        else if (c0 % 4 == 0 && nc == 20)
+        } else if (c0 % 4 == 0 && nc == 20) {
+            RUN(ptv2_kernel_lds((const void *)classifier_fwd_kernel<20>, lds));
             hipLaunchKernelGGL(classifier_fwd_kernel<20>, dim3(gr), dim3(TPB), lds, st, (long long)M->level[0].n, c0,
                                (const float *)A.head.y, M->head_w, M->head_b, M->logits);
-        else
+        } else {
+            RUN(ptv2_kernel_lds((const void *)small_linear_fwd_kernel, lds));
             hipLaunchKernelGGL(small_linear_fwd_kernel, dim3(grid_for((long long)M->level[0].n * nc)), dim3(TPB), lds, st,
                                (long long)M->level[0].n, c0, nc, (const float *)A.head.y, M->head_w, M->head_b, M->logits);
+        }
     }
     PTV2_CHECK_LAUNCH();
     return PTV2_OK;
@@ -694,12 +699,16 @@ int model_backward(const ptv2_model *M, const float *g_logits, void *workspace, 
         hipLaunchKernelGGL(copy4_kernel, dim3(grid_for(n4)), dim3(TPB), 0, st, n4, (const float4 *)g_logits, (float4 *)gb);
     } else {
         const int c0 = M->head.cout, nc = M->num_classes;
-        if (c0 % 4 == 0 && (long long)n0 * (c0 / 4) < (1LL << 31))
-            hipLaunchKernelGGL(small_linear_bwd4_kernel, dim3(grid_for((long long)n0 * (c0 / 4))), dim3(TPB),
-                               sizeof(float) * (size_t)nc * c0, st, (long long)n0, c0, nc, g_logits, M->head_w, (float4 *)ga);
-        else
-            hipLaunchKernelGGL(small_linear_bwd_kernel, dim3(grid_for((long long)n0 * c0)), dim3(TPB), sizeof(float) * (size_t)nc * c0,
-                               st, (long long)n0, c0, nc, g_logits, M->head_w, ga);
+        const size_t lds = sizeof(float) * (size_t)nc * c0;
+        if (c0 % 4 == 0 && (long long)n0 * (c0 / 4) < (1LL << 31)) {
+            RUN(ptv2_kernel_lds((const void *)small_linear_bwd4_kernel, lds));
+            hipLaunchKernelGGL(small_linear_bwd4_kernel, dim3(grid_for((long long)n0 * (c0 / 4))), dim3(TPB), lds, st, (long long)n0, c0,
+                               nc, g_logits, M->head_w, (float4 *)ga);
+        } else {
+            RUN(ptv2_kernel_lds((const void *)small_linear_bwd_kernel, lds));
+            hipLaunchKernelGGL(small_linear_bwd_kernel, dim3(grid_for((long long)n0 * c0)), dim3(TPB), lds, st, (long long)n0, c0, nc,
+                               g_logits, M->head_w, ga);
+        }
         RUN(linear_wgrad_hip_launcher(n0, nc, c0, g_logits, A.head.y, M->g_head_w, M->head_b ? M->g_head_b : nullptr, W.dense, W.dense_bytes, stream));
         RUN(linbn_backward(M, M->head, A.head, n0, dec_in[0], ga, gc, gb, 0, W, stream));
     }

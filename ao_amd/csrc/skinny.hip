@@ -364,16 +364,14 @@ static int skinny_forward_run(int n, int cin, int cout, int sets, const float *c
         const int ntiles = (n + R - 1) / R, cap = std::max(1, 256 * per_cu / sets);
         const int walk = (ntiles + cap - 1) / cap, nblk = (ntiles + walk - 1) / walk;
         auto kernel = xsc[0] ? skinny_fwd_tile_kernel<true> : skinny_fwd_tile_kernel<false>;
-        if (tile_lds > 32 * 1024)
-            (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds);
+        RUN(ptv2_kernel_lds((const void *)kernel, tile_lds));
         hipLaunchKernelGGL(kernel, dim3(nblk, sets), dim3(TPB), tile_lds, st, n, cin, cout, R, ntiles, x[0], W, xsc[0], xsh[0], y[0],
                            x1, sc1, sh1, y1);
         return PTV2_OK;
     }
     const size_t lds = sizeof(float) * ((size_t)cout * (cin + 4) + 2 * (size_t)cin);
     if (lds > 160 * 1024) return PTV2_ERR_ARG;
-    if (lds > 32 * 1024)
-        (void)hipFuncSetAttribute((const void *)skinny_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    RUN(ptv2_kernel_lds((const void *)skinny_fwd_kernel, lds));
     const long long total = (long long)n * cout;
     const int nblk = (int)std::min<long long>((total + TPB - 1) / TPB, 256 * 8);
     hipLaunchKernelGGL(skinny_fwd_kernel, dim3(nblk, sets), dim3(TPB), lds, st, (long long)n, cin, cout, x[0], W, xsc[0], xsh[0], y[0],

@@ -330,9 +330,7 @@ extern "C" int spconv_stem_hip_launcher(int n, int k, int cin, int cout, const f
     if (transpose) {
         hipLaunchKernelGGL(stem_bwd_kernel, dim3(divup((long long)n * cin, 256)), dim3(256), 0, st, n, k, cin, cout, in, tab, weight, out);
     } else {
-        // (more dynamic LDS than the default 64 KB; per device, so asked for on every call)
-        if (hipFuncSetAttribute((const void *)stem_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 147456) != hipSuccess)
-            return PTV2_ERR_LAUNCH;
+        RUN(ptv2_kernel_lds((const void *)stem_kernel, 147456));  // (more dynamic LDS than the default 64 KB)
         const int rp = 256 / cout;
         hipLaunchKernelGGL(stem_kernel, dim3(std::min(divup(n, rp * 8), 1024)), dim3(256), (size_t)lds, st, n, k, cin, cout, in, tab,
                            weight, out);

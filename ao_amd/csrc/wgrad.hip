@@ -604,19 +604,6 @@ constexpr size_t WGRAD_TABLE_BYTES = ptv2_align256(sizeof(WgradJob) * WGRAD_MAX_
 
 // the caller armed the file for this call (rs: the row-scaled strided form and the recompute form)
 bool may_file(bool rs) { return g_wdefer.active && (rs ? g_wdefer.armed_rs : g_wdefer.armed); }
-
-// the LDS-staged kernels ask for more dynamic LDS than the default limit
-bool wgrad_configure() {
-    static const bool ok = [] {
-        const void *kernels[4] = {(const void *)linear_wgrad_lds_kernel<0>, (const void *)linear_wgrad_lds_kernel<1>,
-                                  (const void *)linear_wgrad_lds_kernel_jobs<0>, (const void *)linear_wgrad_lds_kernel_jobs<1>};
-        bool all = true;
-        for (const void *k : kernels)
-            all = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WL_LDS_BYTES) == hipSuccess && all;
-        return all;
-    }();
-    return ok;
-}
 }  // namespace
 
 void ptv2_wgrad_defer_begin(void *arena, size_t bytes) {
@@ -651,7 +638,6 @@ int ptv2_wgrad_defer_flush(void *stream) {
     WgradDefer &D = g_wdefer;
     if (!D.active) return PTV2_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (!wgrad_configure()) return PTV2_ERR_LAUNCH;
     for (int f = 0; f < WGRAD_FORMS; ++f) {
         const WgradForm form = (WgradForm)f;
         std::vector<WgradJob> &jobs = D.jobs[form];
@@ -691,8 +677,14 @@ int ptv2_wgrad_defer_flush(void *stream) {
             const dim3 grid((unsigned)wgs), block(TPB);
             const WgradJob *tab = table;
             switch (form) {
-                case WF_LDS: hipLaunchKernelGGL(linear_wgrad_lds_kernel_jobs<0>, grid, block, WL_LDS_BYTES, st, tab, njobs); break;
-                case WF_LDS_RS: hipLaunchKernelGGL(linear_wgrad_lds_kernel_jobs<1>, grid, block, WL_LDS_BYTES, st, tab, njobs); break;
+                case WF_LDS:  // (the LDS-staged kernels ask for more dynamic LDS than the default limit)
+                    RUN(ptv2_kernel_lds((const void *)linear_wgrad_lds_kernel_jobs<0>, WL_LDS_BYTES));
+                    hipLaunchKernelGGL(linear_wgrad_lds_kernel_jobs<0>, grid, block, WL_LDS_BYTES, st, tab, njobs);
+                    break;
+                case WF_LDS_RS:
+                    RUN(ptv2_kernel_lds((const void *)linear_wgrad_lds_kernel_jobs<1>, WL_LDS_BYTES));
+                    hipLaunchKernelGGL(linear_wgrad_lds_kernel_jobs<1>, grid, block, WL_LDS_BYTES, st, tab, njobs);
+                    break;
                 case WF_DIRECT: hipLaunchKernelGGL(linear_wgrad_kernel_jobs<false>, grid, block, 0, st, tab, njobs); break;
                 case WF_DIRECT_BF16: hipLaunchKernelGGL(linear_wgrad_kernel_jobs<true>, grid, block, 0, st, tab, njobs); break;
                 case WF_GROUPED: {
@@ -767,15 +759,20 @@ static int wgrad_submit(WgradCall &C, bool file, void *workspace, size_t workspa
     // (the recompute form takes as many point splits as fit, never more than a filed job: the same bits either way)
     if (C.form == WF_RECOMPUTE && fit >= 1 && fit < (size_t)J.chunks) (void)gva_wgrad_tile_plan(&J, (int)fit);
     if (fit < (size_t)J.chunks) return PTV2_ERR_WORKSPACE;
-    if (!wgrad_configure()) return PTV2_ERR_LAUNCH;
     hipStream_t st = (hipStream_t)stream;
     J.part = (float *)workspace;
     {
         PtvScopedTimer t(wgrad_kid(C.form), st, C.bytes);
         const dim3 grid(J.chunks, J.tiles, J.batch), block(TPB);
         switch (C.form) {
-            case WF_LDS: hipLaunchKernelGGL(linear_wgrad_lds_kernel<0>, grid, block, WL_LDS_BYTES, st, J); break;
-            case WF_LDS_RS: hipLaunchKernelGGL(linear_wgrad_lds_kernel<1>, grid, block, WL_LDS_BYTES, st, J); break;
+            case WF_LDS:
+                RUN(ptv2_kernel_lds((const void *)linear_wgrad_lds_kernel<0>, WL_LDS_BYTES));
+                hipLaunchKernelGGL(linear_wgrad_lds_kernel<0>, grid, block, WL_LDS_BYTES, st, J);
+                break;
+            case WF_LDS_RS:
+                RUN(ptv2_kernel_lds((const void *)linear_wgrad_lds_kernel<1>, WL_LDS_BYTES));
+                hipLaunchKernelGGL(linear_wgrad_lds_kernel<1>, grid, block, WL_LDS_BYTES, st, J);
+                break;
             case WF_DIRECT: hipLaunchKernelGGL(linear_wgrad_kernel<false>, grid, block, 0, st, J); break;
             case WF_DIRECT_BF16: hipLaunchKernelGGL(linear_wgrad_kernel<true>, grid, block, 0, st, J); break;
             case WF_GROUPED:
