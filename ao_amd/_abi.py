@@ -185,3 +185,10 @@ if not os.path.exists(V2M1_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % V2M1_HEADER)
 with open(V2M1_HEADER) as _f:
     v2m1_consts, v2m1_structs, v2m1_signatures = parse(_f.read())
+
+# the thirteenth public header (SpUNet-v1m1's sparse convolutions with bf16 matrix-core operands), likewise
+SPCONV_BF16_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_spconv_bf16_hip.h")
+if not os.path.exists(SPCONV_BF16_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SPCONV_BF16_HEADER)
+with open(SPCONV_BF16_HEADER) as _f:
+    spconv_bf16_consts, spconv_bf16_structs, spconv_bf16_signatures = parse(_f.read())

@@ -48,6 +48,8 @@ EXPECTED_INSEVAL_ABI = 1
 EXPECTED_CSC_ABI = 1
 # the same for include/ptv2_v2m1_hip.h and ptv2_v2m1_abi_version() (ao_amd/csrc/gva_mul.hip)
 EXPECTED_V2M1_ABI = 1
+# the same for include/ptv2_spconv_bf16_hip.h and ptv2_spconv_bf16_abi_version() (ao_amd/csrc/spconv_bf16.hip)
+EXPECTED_SPCONV_BF16_ABI = 1
 
 
 def build(verbose=False):
@@ -67,7 +69,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures, _abi.pp2s_signatures,
                       _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures, _abi.msc_signatures,
-                      _abi.st_signatures, _abi.inseval_signatures, _abi.csc_signatures, _abi.v2m1_signatures):
+                      _abi.st_signatures, _abi.inseval_signatures, _abi.csc_signatures, _abi.v2m1_signatures,
+                      _abi.spconv_bf16_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -133,6 +136,10 @@ def lib():
         if have != EXPECTED_V2M1_ABI:
             raise RuntimeError("ao_amd: %s has v2m1 ABI version %d, the python side expects %d -- stale build; rebuild with "
                                "`make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_V2M1_ABI))
+        have = handle.ptv2_spconv_bf16_abi_version()
+        if have != EXPECTED_SPCONV_BF16_ABI:
+            raise RuntimeError("ao_amd: %s has spconv bf16 ABI version %d, the python side expects %d -- stale build; rebuild "
+                               "with `make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_SPCONV_BF16_ABI))
         for which, name in enumerate(("ptv1_params", "ptv1_norms", "ptv1_grads")):
             if handle.ptv2_ptv1_struct_bytes(which) != ctypes.sizeof(_abi.ptv1_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

@@ -11,7 +11,9 @@ KRSC layout); the execution differs:
   * BatchNorm, ReLU and the residual tail are RowBatchNorm1d / bn_residual_relu (ao_amd/ptv2/layers.py);
   * every sum has a fixed order: two identical steps give the same bits.
 
-`cls_mode=True` is not implemented.  fp32 only: under torch.autocast the nodes take fp32 inputs.
+`cls_mode=True` is not implemented.  `conv_operands` ("fp32", the default: exact fp32 whatever autocast says; "bf16";
+"autocast": bf16 exactly when CUDA autocast is on at the call) chooses the operand form of the k > 1 matrix-core convolutions
+(ao_amd/spunet/conv.py); the stem and the 1 x 1 x 1 convolutions are fp32 on their own paths.  It is not part of the state dict.
 """
 import math
 from collections import OrderedDict
@@ -39,8 +41,12 @@ class SparseTensor:
 class _SparseConv(nn.Module):
     kind = None
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None,
+                 conv_operands="fp32"):
         super().__init__()
+        if conv_operands not in conv.OPERANDS:
+            raise ValueError("ao_amd spunet: conv_operands must be one of %s, got %r" % (", ".join(map(repr, conv.OPERANDS)), conv_operands))
+        self.conv_operands = conv_operands
         self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
         self.stride, self.padding, self.indice_key = stride, padding, indice_key
         k = kernel_size
@@ -73,10 +79,11 @@ class SubMConv3d(_SparseConv):
     """Outputs at the input voxels, in input order; the kernel is centred whatever `padding` says.  kernel_size 1 is a row
     Linear on the (Cout, Cin) view of the weight."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None,
+                 conv_operands="fp32"):
         if kernel_size not in (1, 3, 5):
             raise ValueError("ao_amd spunet: SubMConv3d kernel sizes are 1, 3 and 5")
-        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, indice_key)
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, indice_key, conv_operands)
         self.kind = "subm5" if kernel_size == 5 else "subm3"
 
     def forward(self, x):
@@ -91,23 +98,25 @@ class SubMConv3d(_SparseConv):
         level = self._table(x)
         if level != x.level:
             raise ValueError("ao_amd spunet: indice_key %r is level %d, the input is level %d" % (self.indice_key, level, x.level))
-        return x.replace_feature(self._add_bias(conv.subm_conv(f, self.weight, x.tables, level, self.kernel_size)))
+        return x.replace_feature(self._add_bias(conv.subm_conv(f, self.weight, x.tables, level, self.kernel_size,
+                                                               self.conv_operands)))
 
 
 class SparseConv3d(_SparseConv):
     """kernel_size 2, stride 2: one output per occupied coarse voxel coord >> 1, in ascending (cloud, x, y, z) order"""
     kind = "down"
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None,
+                 conv_operands="fp32"):
         if kernel_size != 2 or stride != 2:
             raise ValueError("ao_amd spunet: SparseConv3d is kernel_size 2, stride 2")
-        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, indice_key)
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, indice_key, conv_operands)
 
     def forward(self, x):
         level = x.level if self.indice_key is None else self._table(x)
         if level != x.level or level + 1 >= LEVELS:
             raise ValueError("ao_amd spunet: indice_key %r downsamples level %d, the input is level %d" % (self.indice_key, level, x.level))
-        y = conv.down_conv(x.features, self.weight, x.tables, level)
+        y = conv.down_conv(x.features, self.weight, x.tables, level, self.conv_operands)
         return SparseTensor(self._add_bias(y), x.tables, level + 1)
 
 
@@ -115,16 +124,16 @@ class SparseInverseConv3d(_SparseConv):
     """kernel_size 2: the table of the SparseConv3d with the same indice_key, the other way"""
     kind = "down"
 
-    def __init__(self, in_channels, out_channels, kernel_size, bias=False, indice_key=None):
+    def __init__(self, in_channels, out_channels, kernel_size, bias=False, indice_key=None, conv_operands="fp32"):
         if kernel_size != 2:
             raise ValueError("ao_amd spunet: SparseInverseConv3d is kernel_size 2")
-        super().__init__(in_channels, out_channels, kernel_size, 1, 0, bias, indice_key)
+        super().__init__(in_channels, out_channels, kernel_size, 1, 0, bias, indice_key, conv_operands)
 
     def forward(self, x):
         level = x.level - 1 if self.indice_key is None else self._table(x)
         if level != x.level - 1 or level < 0:
             raise ValueError("ao_amd spunet: indice_key %r leads back to level %d, the input is level %d" % (self.indice_key, level, x.level))
-        y = conv.inverse_conv(x.features, self.weight, x.tables, level)
+        y = conv.inverse_conv(x.features, self.weight, x.tables, level, self.conv_operands)
         return SparseTensor(self._add_bias(y), x.tables, level)
 
 
@@ -151,18 +160,19 @@ class SparseSequential(nn.Sequential):
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, in_channels, embed_channels, stride=1, norm_fn=None, indice_key=None, bias=False):
+    def __init__(self, in_channels, embed_channels, stride=1, norm_fn=None, indice_key=None, bias=False, conv_operands="fp32"):
         super().__init__()
         assert norm_fn is not None
         if in_channels == embed_channels:
             self.proj = SparseSequential(nn.Identity())
         else:
             self.proj = SparseSequential(SubMConv3d(in_channels, embed_channels, kernel_size=1, bias=False), norm_fn(embed_channels))
-        self.conv1 = SubMConv3d(in_channels, embed_channels, kernel_size=3, stride=stride, padding=1, bias=bias, indice_key=indice_key)
+        self.conv1 = SubMConv3d(in_channels, embed_channels, kernel_size=3, stride=stride, padding=1, bias=bias, indice_key=indice_key,
+                                conv_operands=conv_operands)
         self.bn1 = norm_fn(embed_channels)
         self.relu = nn.ReLU()
         self.conv2 = SubMConv3d(embed_channels, embed_channels, kernel_size=3, stride=stride, padding=1, bias=bias,
-                                indice_key=indice_key)
+                                indice_key=indice_key, conv_operands=conv_operands)
         self.bn2 = norm_fn(embed_channels)
         self.stride = stride
 
@@ -179,7 +189,7 @@ def _norm(channels):
 
 class SpUNetBase(nn.Module):
     def __init__(self, in_channels, num_classes, base_channels=32, channels=(32, 64, 128, 256, 256, 128, 96, 96),
-                 layers=(2, 3, 4, 6, 2, 2, 2, 2), cls_mode=False):
+                 layers=(2, 3, 4, 6, 2, 2, 2, 2), cls_mode=False, conv_operands="fp32"):
         super().__init__()
         assert len(layers) % 2 == 0
         assert len(layers) == len(channels)
@@ -188,29 +198,31 @@ class SpUNetBase(nn.Module):
         self.in_channels, self.num_classes, self.base_channels = in_channels, num_classes, base_channels
         self.channels, self.layers = channels, layers
         self.num_stages = len(layers) // 2
-        self.cls_mode = cls_mode
+        self.cls_mode, self.conv_operands = cls_mode, conv_operands
         if self.num_stages > LEVELS - 1:
             raise ValueError("ao_amd spunet: at most %d stages (include/ptv2_spconv_hip.h: SPCONV_LEVELS)" % (LEVELS - 1))
         norm_fn, block = _norm, BasicBlock
         self.conv_input = SparseSequential(
-            SubMConv3d(in_channels, base_channels, kernel_size=5, padding=1, bias=False, indice_key="stem"),
+            SubMConv3d(in_channels, base_channels, kernel_size=5, padding=1, bias=False, indice_key="stem", conv_operands=conv_operands),
             norm_fn(base_channels), nn.ReLU())
         enc_channels, dec_channels = base_channels, channels[-1]
         self.down, self.up, self.enc, self.dec = nn.ModuleList(), nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
         for s in range(self.num_stages):
             self.down.append(SparseSequential(
-                SparseConv3d(enc_channels, channels[s], kernel_size=2, stride=2, bias=False, indice_key="spconv%d" % (s + 1)),
+                SparseConv3d(enc_channels, channels[s], kernel_size=2, stride=2, bias=False, indice_key="spconv%d" % (s + 1),
+                             conv_operands=conv_operands),
                 norm_fn(channels[s]), nn.ReLU()))
             self.enc.append(SparseSequential(OrderedDict(
-                ("block%d" % i, block(channels[s], channels[s], norm_fn=norm_fn, indice_key="subm%d" % (s + 1)))
+                ("block%d" % i, block(channels[s], channels[s], norm_fn=norm_fn, indice_key="subm%d" % (s + 1),
+                                      conv_operands=conv_operands))
                 for i in range(layers[s]))))
             self.up.append(SparseSequential(
                 SparseInverseConv3d(channels[len(channels) - s - 2], dec_channels, kernel_size=2, bias=False,
-                                    indice_key="spconv%d" % (s + 1)),
+                                    indice_key="spconv%d" % (s + 1), conv_operands=conv_operands),
                 norm_fn(dec_channels), nn.ReLU()))
             self.dec.append(SparseSequential(OrderedDict(
                 ("block%d" % i, block(dec_channels + enc_channels if i == 0 else dec_channels, dec_channels, norm_fn=norm_fn,
-                                      indice_key="subm%d" % s))
+                                      indice_key="subm%d" % s, conv_operands=conv_operands))
                 for i in range(layers[len(channels) - s - 1]))))
             enc_channels = channels[s]
             dec_channels = channels[len(channels) - s - 2]
