@@ -192,3 +192,11 @@ if not os.path.exists(SPCONV_BF16_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SPCONV_BF16_HEADER)
 with open(SPCONV_BF16_HEADER) as _f:
     spconv_bf16_consts, spconv_bf16_structs, spconv_bf16_signatures = parse(_f.read())
+
+# the fourteenth public header (OctFormer's octree attention blocks: neighbour table, fused dilated patch attention, depthwise
+# octree convolution), likewise
+OCT_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_oct_hip.h")
+if not os.path.exists(OCT_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % OCT_HEADER)
+with open(OCT_HEADER) as _f:
+    oct_consts, oct_structs, oct_signatures = parse(_f.read())

@@ -1,0 +1,177 @@
+"""OctFormer's two hot operators on ao_amd/csrc/oct_attention.hip and oct_dwconv.hip (C ABI include/ptv2_oct_hip.h; DESIGN.md
+section 19), each one autograd node.
+
+`octree_attention` is OctreeAttention.forward between the qkv projection and the output projection: the dilated patch partition,
+the logits with the three-axis relative-position bias, the per-cloud mask, the row softmax, the aggregation and the reverse
+partition, without a padded or transposed copy of the nodes, a mask, an index tensor or a (P, H, K, K) tensor.  It saves out and
+the row log-sum-exp (n, H).  `octree_dwconv` is the depthwise convolution over the 27-neighbour table.
+
+AO_AMD_OCTFORMER (read on every call): unset or "hip": the kernels; "torch": the reference's eager statements on the device.
+"""
+import os
+
+import torch
+
+from .. import _lib
+from .octree import C as CONSTS, OctreeLevel, run
+
+MAX_PATCH, MAX_HEADS, MAX_RPE, MAX_CHANNELS = (CONSTS[k] for k in ("OCT_MAX_PATCH", "OCT_MAX_HEADS", "OCT_MAX_RPE", "OCT_MAX_CHANNELS"))
+
+
+def mode():
+    m = os.environ.get("AO_AMD_OCTFORMER", "hip")
+    if m not in ("hip", "torch"):
+        raise ValueError("ao_amd octformer: AO_AMD_OCTFORMER=%r (hip or torch)" % m)
+    return m
+
+
+def pos_bnd_of(patch_size, dilation):
+    return int(0.8 * patch_size * dilation ** 0.5)
+
+
+# ------------------------------------------------------------------------------------------------------- attention ----
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, qkv, table, level, patch, dilation, scale):
+        qkv, table = qkv.contiguous(), table.contiguous()
+        n, h = qkv.shape[0], table.shape[1]
+        c = qkv.shape[1] // 3
+        out = torch.empty((n, c), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((n, h), dtype=torch.float32, device=qkv.device)
+        ctx.shape = dict(n=n, c=c, h=h, hd=c // h, patch=patch, dilation=dilation, pos_bnd=pos_bnd_of(patch, dilation),
+                         scale=float(scale))
+        ctx.level = level
+        run("oct_attention_fwd_hip_launcher", "octree_attention", xyz=level.xyz, batch=level.batch, qkv=qkv, table=table, out=out,
+            lse=lse, **ctx.shape)
+        ctx.save_for_backward(qkv, table, out, lse)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        qkv, table, out, lse = ctx.saved_tensors
+        s, level = ctx.shape, ctx.level
+        g = g.contiguous()
+        g_qkv, g_table = torch.empty_like(qkv), torch.empty_like(table)
+        need = _lib.lib().ptv2_oct_workspace_bytes(s["n"], s["patch"], s["dilation"], s["h"], 2 * s["pos_bnd"] + 1)
+        ws = _lib.workspace(need, qkv.device)
+        run("oct_attention_bwd_hip_launcher", "octree_attention", xyz=level.xyz, batch=level.batch, qkv=qkv, table=table, out=out,
+            lse=lse, g_out=g, g_qkv=g_qkv, g_table=g_table, workspace=ws, workspace_bytes=ws.numel(), **s)
+        return g_qkv, g_table, None, None, None, None
+
+
+def octree_attention_torch(qkv, xyz, batch, clouds, table, patch_size, dilation, scale):
+    """OctreeT.build_t and OctreeAttention.forward (octformer_v1m1_base.py:56-99, :165-176, :212-245) in eager statements on a
+    qkv that is already projected, for any dtype.  The padded rows are zeros where the reference's carry the qkv bias: they
+    attend only each other and patch_reverse cuts them off."""
+    K, D, H = patch_size, dilation, table.shape[1]
+    n, C = qkv.shape[0], qkv.shape[1] // 3
+    num = -(-n // (K * D)) * (K * D) - n
+    pos_bnd = pos_bnd_of(K, D)
+    rpe_num = 2 * pos_bnd + 1
+
+    def patch_partition(data, fill_value=0):
+        return torch.cat([data, data.new_full((num,) + data.shape[1:], fill_value)], dim=0)
+
+    batch, xyz, data = patch_partition(batch.long(), clouds), patch_partition(xyz.long()), patch_partition(qkv)
+    if D > 1:
+        mask = batch.view(-1, K, D).transpose(1, 2).reshape(-1, K)
+        xyz = xyz.view(-1, K, D, 3).transpose(1, 2).reshape(-1, K, 3)
+        data = data.view(-1, K, D, 3 * C).transpose(1, 2).reshape(-1, 3 * C)
+    else:
+        mask, xyz = batch.view(-1, K), xyz.view(-1, K, 3)
+    mask = mask.unsqueeze(2) - mask.unsqueeze(1)
+    mask = mask.masked_fill(mask != 0, -1e3)
+    rel_pos = xyz.unsqueeze(2) - xyz.unsqueeze(1)
+
+    q, k, v = data.reshape(-1, K, 3, H, C // H).permute(2, 0, 3, 1, 4)
+    q = q * scale
+    attn = q @ k.transpose(-2, -1)
+    idx = rel_pos.clamp(-pos_bnd, pos_bnd) + (pos_bnd + torch.arange(3, device=xyz.device) * rpe_num)
+    rpe = table.index_select(0, idx.reshape(-1)).view(idx.shape + (-1,)).sum(3).permute(0, 3, 1, 2)
+    attn = torch.softmax(attn + rpe + mask.unsqueeze(1), dim=-1)
+    data = (attn @ v).transpose(1, 2).reshape(-1, C)
+    if D > 1:
+        data = data.view(-1, D, K, C).transpose(1, 2).reshape(-1, C)
+    return data[:n]
+
+
+def octree_attention(qkv, level, table, patch_size, dilation, scale):
+    """(n, C) from qkv (n, 3 C) in the order of `level`, columns [3][H][hd], and the table (3 R, H), R = 2 pos_bnd + 1,
+    pos_bnd = int(0.8 K sqrt(D)).  fp32, under autocast too."""
+    _lib.require_cuda(qkv, table)
+    if not isinstance(level, OctreeLevel):
+        raise TypeError("ao_amd octformer: octree_attention takes the OctreeLevel of octree_level()")
+    K, D = int(patch_size), int(dilation)
+    if not 1 <= K <= MAX_PATCH:
+        raise ValueError("ao_amd octformer: patch_size %d outside [1, %d]" % (K, MAX_PATCH))
+    if D < 1:
+        raise ValueError("ao_amd octformer: dilation %d; at least 1" % D)
+    R = 2 * pos_bnd_of(K, D) + 1
+    if R > MAX_RPE:
+        raise ValueError("ao_amd octformer: patch_size %d with dilation %d has %d table rows per axis; at most %d" % (K, D, R, MAX_RPE))
+    if table.dim() != 2 or table.shape[0] != 3 * R:
+        raise ValueError("ao_amd octformer: the table of patch_size %d, dilation %d is (%d, H); got %s" % (K, D, 3 * R, tuple(table.shape)))
+    H = table.shape[1]
+    if not 1 <= H <= MAX_HEADS:
+        raise ValueError("ao_amd octformer: %d heads; at most %d" % (H, MAX_HEADS))
+    if qkv.dim() != 2 or qkv.shape[0] != level.n or qkv.shape[1] % (3 * H):
+        raise ValueError("ao_amd octformer: qkv is (n, 3 C) with n = %d and C a multiple of %d heads; got %s" % (level.n, H, tuple(qkv.shape)))
+    hd = qkv.shape[1] // (3 * H)
+    if hd not in (16, 32):
+        raise ValueError("ao_amd octformer: %d channels per head; 16 or 32" % hd)
+    if mode() == "torch":
+        with torch.autocast("cuda", enabled=False):
+            return octree_attention_torch(qkv.float(), level.xyz, level.batch, level.clouds, table.float(), K, D, scale)
+    return _Attention.apply(qkv, table, level, K, D, scale)
+
+
+# ----------------------------------------------------------------------------------------------------- convolution ----
+class _DWConv(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, weights, level):
+        x, w = x.contiguous(), weights.contiguous()
+        y = torch.empty_like(x)
+        run("oct_dwconv_fwd_hip_launcher", "octree_dwconv", n=x.shape[0], c=x.shape[1], nbr=level.nbr, x=x, w=w, y=y)
+        ctx.save_for_backward(x, w)
+        ctx.level = level
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        (n, c), g = x.shape, g.contiguous()
+        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        g_w = torch.empty_like(w) if ctx.needs_input_grad[1] else None
+        ws = _lib.workspace(_lib.lib().ptv2_oct_dwconv_workspace_bytes(n, c), x.device)
+        run("oct_dwconv_bwd_hip_launcher", "octree_dwconv", n=n, c=c, nbr=ctx.level.nbr, x=x, w=w, g_y=g, g_x=_lib.ptr(g_x),
+            g_w=_lib.ptr(g_w), workspace=ws, workspace_bytes=ws.numel())
+        return g_x, g_w, None
+
+
+def octree_dwconv_torch(x, weights, nbr):
+    """the 27 slots one after the other, for any dtype"""
+    y = torch.zeros_like(x)
+    for k in range(27):
+        j = nbr[:, k].long()
+        y = y + weights[k, 0] * torch.where((j >= 0).unsqueeze(1), x[j.clamp(min=0)], torch.zeros_like(x))
+    return y
+
+
+def octree_dwconv(x, weights, level):
+    """(n, C): y[i, c] = sum_k weights[k, 0, c] x[nbr[i, k], c] over the 27 neighbours of `level`, missing ones skipped."""
+    _lib.require_cuda(x, weights)
+    if not isinstance(level, OctreeLevel):
+        raise TypeError("ao_amd octformer: octree_dwconv takes the OctreeLevel of octree_level()")
+    if x.dim() != 2 or x.shape[0] != level.n or tuple(weights.shape) != (27, 1, x.shape[1]):
+        raise ValueError("ao_amd octformer: octree_dwconv takes x (n, C) with n = %d and weights (27, 1, C); got %s %s"
+                         % (level.n, tuple(x.shape), tuple(weights.shape)))
+    if x.shape[1] % 4 or not 4 <= x.shape[1] <= MAX_CHANNELS:
+        raise ValueError("ao_amd octformer: %d channels; a multiple of 4, at most %d" % (x.shape[1], MAX_CHANNELS))
+    if mode() == "torch":
+        with torch.autocast("cuda", enabled=False):
+            return octree_dwconv_torch(x.float(), weights.float(), level.nbr)
+    return _DWConv.apply(x, weights, level)
