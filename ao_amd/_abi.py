@@ -200,3 +200,10 @@ if not os.path.exists(OCT_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % OCT_HEADER)
 with open(OCT_HEADER) as _f:
     oct_consts, oct_structs, oct_signatures = parse(_f.read())
+
+# the fifteenth public header (SPVCNN's point branch: the point-voxel map, trilinear devoxelize, voxelize), likewise
+SPV_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_spv_hip.h")
+if not os.path.exists(SPV_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SPV_HEADER)
+with open(SPV_HEADER) as _f:
+    spv_consts, spv_structs, spv_signatures = parse(_f.read())

@@ -33,7 +33,7 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, H
     segmentor and `Criteria` then builds it from the same config entry; with TEST (pointcept/engines/test.py:26) the whole-scene
     tester of ao_amd/ptv2/tester.py under "SemSegTester", which `test = dict(type="SemSegTester")` then resolves to.  Every
     registry may be omitted.  MODELS also receives
-    CACSegmentor under "CAC-v1m1", PointTransformerV2M1 under "PT-v2m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", PointGroup under "PG-v1m1", MaskedSceneContrast
+    CACSegmentor under "CAC-v1m1", PointTransformerV2M1 under "PT-v2m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", SPVCNN under "SPVCNN", PointGroup under "PG-v1m1", MaskedSceneContrast
     under "MSC-v1m1", MaskedSceneContrastCSC under "MSC-v1m2" and StratifiedTransformer under "ST-v1m2" and "STv1m2"; the returned
     list of names leaves those entries out (it predates them).  With HOOKS (pointcept/engines/hooks/builder.py) the instance
     evaluator of ao_amd/pointgroup/evaluate.py is filed under "InsSegEvaluator", likewise not listed."""
@@ -63,6 +63,10 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, H
         from ..spunet import SpUNetBase
 
         _register(MODELS, SpUNetBase, "SpUNet-v1m1", force)
+        # SPVCNN (ao_amd/spvcnn), likewise filed and not listed
+        from ..spvcnn import SPVCNN
+
+        _register(MODELS, SPVCNN, "SPVCNN", force)
         # PointGroup (ao_amd/pointgroup), likewise filed and not listed
         from ..pointgroup import PointGroup
 
