@@ -207,3 +207,10 @@ if not os.path.exists(SPV_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SPV_HEADER)
 with open(SPV_HEADER) as _f:
     spv_consts, spv_structs, spv_signatures = parse(_f.read())
+
+# the sixteenth public header (Swin3D's window attention with cRSE: the window map, the fused sparse window attention), likewise
+SWIN_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_swin_hip.h")
+if not os.path.exists(SWIN_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SWIN_HEADER)
+with open(SWIN_HEADER) as _f:
+    swin_consts, swin_structs, swin_signatures = parse(_f.read())
