@@ -214,3 +214,10 @@ if not os.path.exists(SWIN_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SWIN_HEADER)
 with open(SWIN_HEADER) as _f:
     swin_consts, swin_structs, swin_signatures = parse(_f.read())
+
+# the seventeenth public header (Swin3D's window attention on half-precision storage: fp16_mode 1), likewise
+SWIN_F16_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_swin_f16_hip.h")
+if not os.path.exists(SWIN_F16_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SWIN_F16_HEADER)
+with open(SWIN_F16_HEADER) as _f:
+    swin_f16_consts, swin_f16_structs, swin_f16_signatures = parse(_f.read())

@@ -56,6 +56,8 @@ EXPECTED_OCT_ABI = 1
 EXPECTED_SPV_ABI = 1
 # the same for include/ptv2_swin_hip.h and ptv2_swin_abi_version() (ao_amd/csrc/swin_attention.hip)
 EXPECTED_SWIN_ABI = 1
+# the same for include/ptv2_swin_f16_hip.h and ptv2_swin_f16_abi_version() (ao_amd/csrc/swin_attention_f16.hip)
+EXPECTED_SWIN_F16_ABI = 1
 
 
 def build(verbose=False):
@@ -76,7 +78,8 @@ def lib():
         for table in (_SIGNATURES, _abi.data_signatures, _abi.refine_signatures, _abi.pp2s_signatures,
                       _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures, _abi.msc_signatures,
                       _abi.st_signatures, _abi.inseval_signatures, _abi.csc_signatures, _abi.v2m1_signatures,
-                      _abi.spconv_bf16_signatures, _abi.oct_signatures, _abi.spv_signatures, _abi.swin_signatures):
+                      _abi.spconv_bf16_signatures, _abi.oct_signatures, _abi.spv_signatures, _abi.swin_signatures,
+                      _abi.swin_f16_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -167,6 +170,13 @@ def lib():
         if handle.ptv2_swin_struct_bytes(0) != ctypes.sizeof(_abi.swin_structs["swin_args"]):
             raise RuntimeError("ao_amd: swin_args is %d bytes in python, %d in %s (stale build)" % (
                 ctypes.sizeof(_abi.swin_structs["swin_args"]), handle.ptv2_swin_struct_bytes(0), LIB_PATH))
+        have = handle.ptv2_swin_f16_abi_version()
+        if have != EXPECTED_SWIN_F16_ABI:
+            raise RuntimeError("ao_amd: %s has swin f16 ABI version %d, the python side expects %d -- stale build; rebuild "
+                               "with `make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_SWIN_F16_ABI))
+        if handle.ptv2_swin_f16_struct_bytes(0) != ctypes.sizeof(_abi.swin_f16_structs["swin_f16_args"]):
+            raise RuntimeError("ao_amd: swin_f16_args is %d bytes in python, %d in %s (stale build)" % (
+                ctypes.sizeof(_abi.swin_f16_structs["swin_f16_args"]), handle.ptv2_swin_f16_struct_bytes(0), LIB_PATH))
         for which, name in enumerate(("ptv1_params", "ptv1_norms", "ptv1_grads")):
             if handle.ptv2_ptv1_struct_bytes(which) != ctypes.sizeof(_abi.ptv1_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

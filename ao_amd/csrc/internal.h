@@ -125,3 +125,6 @@ int gva_wgrad_tile_supported(int k, int c, int g);
 size_t gva_wgrad_tile_plan(dense::WgradJob *J, int max_splits);
 int gva_wgrad_tile_launch_one(const dense::WgradJob &J, hipStream_t st);
 int gva_wgrad_tile_launch_jobs(const dense::WgradJob *table, int njobs, int wgs, int pos_wgs, hipStream_t st);
+// ---- swin_attention.hip -----------------------------------------------------------------------------------------------
+// g_X_table = the sum over the chunks' (3, R, hd) partials of a head, ascending (one launch; swin_attention_f16.hip shares it)
+int swin_table_reduce(int chunks, int R, int H, int hd, const float *part, float *gq, float *gk, float *gv, void *stream);

@@ -4,7 +4,10 @@ reference's constructor arguments and state-dict keys, on the operators of ops.p
 BasicLayer.forward(feats, grid_coord, batch, local_xyz, colors) replaces the reference's (sp, coords_sp) pair of MinkowskiEngine
 tensors: `feats` (n, C); `grid_coord` (n, 3) integer voxel coordinates at the level's own stride 1; `batch` (n); `local_xyz`
 (n, 3) the sub-voxel offset of the point, in voxels; `colors` (n, 3 or 6) colour and normal in [-1, 1].  It returns the features.
-LayerNorm, the Linears, GELU and the residuals stay torch.  `fp16_mode` is accepted and ignored: the attention is fp32.
+LayerNorm, the Linears, GELU and the residuals stay torch.  `fp16_mode` is handed to crse_attention: with 1 ("fp16 forward and
+fp32 backward") or 2 the attention runs on half-precision storage wherever the qkv Linear wrote float16, i.e. under fp16 autocast
+(DESIGN.md section 22); 2 ("fp16 both ways") takes the same path as 1, a half-precision backward is not built.  With 0, or
+outside autocast, the attention is fp32.
 """
 import torch
 from torch import nn
@@ -73,7 +76,7 @@ class WindowAttention(nn.Module):
     def forward(self, feats, attn_args):
         wmap, signals = attn_args
         out = crse_attention(self.qkv(feats), wmap, signals, self.tables("query"), self.tables("key"), self.tables("value"),
-                             self.table_rows, self.scale, self.num_heads)
+                             self.table_rows, self.scale, self.num_heads, fp16_mode=self.fp16_mode)
         return self.proj(out)
 
 

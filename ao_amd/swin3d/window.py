@@ -17,8 +17,8 @@ ARGS = _abi.swin_structs["swin_args"]
 MAX_WINDOW = C["SWIN_MAX_WINDOW"]
 
 
-def run(launcher, what, **fields):
-    a = ARGS()
+def run(launcher, what, struct=ARGS, **fields):
+    a = struct()
     for name, value in fields.items():
         if name == "rows":
             for s, v in enumerate(value):
