@@ -11,7 +11,8 @@
 // Reductions over rows: every workgroup owns a chunk of CHUNK rows of ONE scene (grid = chunks per scene x scenes, the
 // chunk count from the host's largest scene) and writes a partial slab; a second launch adds the slabs in a fixed order.
 // Results are bitwise reproducible from run to run.  The softmax weights are recomputed in the backward (an N x K matrix
-// is 240 MB at 300 k rows and K = 200).  Limits: K <= 256, C % 4 == 0, C <= 64.
+// is 240 MB at 300 k rows and K = 200).  Limits: K <= 256, C % 4 == 0, C <= 64 for the kernels of this file; 64 < C <= 128 is
+// cac_mfma.hip (the same contract on the matrix cores), which the launchers below forward to.
 #include <algorithm>
 
 #include "common.h"
@@ -558,7 +559,7 @@ __global__ __launch_bounds__(TPB) void distill_backward_kernel(int n, int K, con
     }
 }
 
-bool dims_ok(int K, int C) { return K >= 1 && K <= MAXK && C >= 4 && C <= MAXC && C % 4 == 0; }
+bool dims_ok(int K, int C) { return (K >= 1 && K <= MAXK && C >= 4 && C <= MAXC && C % 4 == 0) || cac_wide_ok(K, C); }
 int chunks_of(int max_rows) { return max_rows > 0 ? divup(max_rows, CHUNK) : 1; }
 }  // namespace
 
@@ -581,7 +582,8 @@ extern "C" int cac_weighted_sum_forward_hip_launcher(int mode, int n, int b, int
     hipStream_t st = (hipStream_t)stream;
     const int J = chunks_of(max_rows);
     float *part = (float *)workspace;
-    hipLaunchKernelGGL(wsum_partial_kernel, dim3(J, b), dim3(TPB), 0, st, mode, k, c, J, x, logits, label, offset, thr, part);
+    if (c > MAXC) RUN(cac_wide_wsum_partial(mode, b, max_rows, k, c, x, logits, label, offset, thr, part, stream));
+    else hipLaunchKernelGGL(wsum_partial_kernel, dim3(J, b), dim3(TPB), 0, st, mode, k, c, J, x, logits, label, offset, thr, part);
     const int nsets = mode == 0 ? b : 1, per = mode == 0 ? J : b * J;
     hipLaunchKernelGGL(wsum_finalize_kernel, dim3(divup((long long)nsets * k * (c + 1), TPB)), dim3(TPB), 0, st, k, c, nsets, per,
                        (const float *)part, eps, z, out);
@@ -596,6 +598,8 @@ extern "C" int cac_weighted_sum_backward_hip_launcher(int mode, int n, int b, in
     if ((mode != 0 && mode != 1) || n < 1 || b < 1 || max_rows < 1 || !dims_ok(k, c) || !x || !offset || !z || !dout || !gx ||
         (mode == 0 && !logits) || (mode == 1 && (!label || glogits)) || (glogits && !out))
         return PTV2_ERR_ARG;
+    if (c > MAXC)
+        return cac_wide_wsum_backward(mode, b, max_rows, k, c, x, logits, label, offset, thr, eps, z, out, dout, gx, glogits, stream);
     hipLaunchKernelGGL(wsum_backward_kernel, dim3(chunks_of(max_rows), b), dim3(TPB), 0, (hipStream_t)stream, mode, k, c, x, logits,
                        label, offset, thr, eps, z, out, dout, gx, glogits);
     PTV2_CHECK_LAUNCH();
@@ -605,6 +609,7 @@ extern "C" int cac_weighted_sum_backward_hip_launcher(int mode, int n, int b, in
 extern "C" int cac_cosine_forward_hip_launcher(int n, int b, int max_rows, int k, int c, const float *x, const float *q,
                                                int per_scene, const int *offset, float scale, float *out, void *stream) {
     if (n < 1 || b < 1 || max_rows < 1 || !dims_ok(k, c) || !x || !q || !offset || !out) return PTV2_ERR_ARG;
+    if (c > MAXC) return cac_wide_cos_forward(b, max_rows, k, c, x, q, per_scene, offset, scale, out, stream);
     hipLaunchKernelGGL(cos_forward_kernel, dim3(chunks_of(max_rows), b), dim3(TPB), 0, (hipStream_t)stream, k, c, x, q, per_scene,
                        offset, scale, out);
     PTV2_CHECK_LAUNCH();
@@ -619,6 +624,7 @@ extern "C" int cac_cosine_backward_hip_launcher(int n, int b, int max_rows, int 
     hipStream_t st = (hipStream_t)stream;
     const int J = chunks_of(max_rows);
     float *part = (float *)workspace;
+    if (c > MAXC) return cac_wide_cos_backward(b, max_rows, k, c, x, q, per_scene, offset, scale, dout, gx, gq, part, stream);
     hipLaunchKernelGGL(cos_backward_kernel, dim3(J, b), dim3(TPB), 0, st, k, c, J, x, q, per_scene, offset, scale, dout, gx, part);
     hipLaunchKernelGGL(cos_proto_finalize_kernel, dim3(k, per_scene ? b : 1), dim3(64), 0, st, k, c, per_scene ? J : b * J,
                        (const float *)part, q, gq);

@@ -125,6 +125,18 @@ int gva_wgrad_tile_supported(int k, int c, int g);
 size_t gva_wgrad_tile_plan(dense::WgradJob *J, int max_splits);
 int gva_wgrad_tile_launch_one(const dense::WgradJob &J, hipStream_t st);
 int gva_wgrad_tile_launch_jobs(const dense::WgradJob *table, int njobs, int wgs, int pos_wgs, hipStream_t st);
+// ---- cac_mfma.hip: cac.hip's heads for 64 < C <= 128 (arguments checked by cac.hip's launchers) -------------------------
+int cac_wide_ok(int k, int c);
+// the slabs of the weighted sums into part (cac.hip's layout; its finalize follows)
+int cac_wide_wsum_partial(int mode, int b, int max_rows, int k, int c, const float *x, const float *logits, const long long *label,
+                          const int *offset, float thr, float *part, void *stream);
+int cac_wide_wsum_backward(int mode, int b, int max_rows, int k, int c, const float *x, const float *logits, const long long *label,
+                           const int *offset, float thr, float eps, const float *z, const float *out, const float *dout, float *gx,
+                           float *glogits, void *stream);
+int cac_wide_cos_forward(int b, int max_rows, int k, int c, const float *x, const float *q, int per_scene, const int *offset,
+                         float scale, float *out, void *stream);
+int cac_wide_cos_backward(int b, int max_rows, int k, int c, const float *x, const float *q, int per_scene, const int *offset,
+                          float scale, const float *dout, float *gx, float *gq, float *part, void *stream);
 // ---- swin_attention.hip -----------------------------------------------------------------------------------------------
 // g_X_table = the sum over the chunks' (3, R, hd) partials of a head, ascending (one launch; swin_attention_f16.hip shares it)
 int swin_table_reduce(int chunks, int R, int H, int hd, const float *part, float *gq, float *gk, float *gv, void *stream);

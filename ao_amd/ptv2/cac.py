@@ -9,7 +9,8 @@ the backbone head's logits and the REFINED logits as `seg_logits`; eval without 
 
 The reference's heads loop in python over every present class (twice, after two `target.unique()` host synchronisations)
 and over the scenes with device-tensor slice bounds.  Here the soft prototypes, the class means, the cosine logits and the
-distillation loss are ao_amd/csrc/cac.hip: a fixed number of launches whatever the class count, no host synchronisation.
+distillation loss are ao_amd/csrc/cac.hip (C <= 64) and ao_amd/csrc/cac_mfma.hip (64 < C <= 128, the products on the matrix
+cores): a fixed number of launches whatever the class count, no host synchronisation.
 Scene bounds come from `input_dict["offset_host"]` when present (no synchronisation), else from ONE `offset.tolist()`.
 
 Kept quirks: the ignore label of the CAC heads is -1 whatever the criteria's `ignore_index` (:78-80, :162-180);
@@ -20,7 +21,8 @@ of an ignored row puts its one-hot half on class 0 (its entropy weight is 0).
 Deviation: under autocast the CAC kernels take fp32 inputs (`custom_fwd(cast_inputs=torch.float32)`) where the reference
 forms the prototype and cosine products in half precision.
 
-The HIP path covers CUDA inputs with K <= 256 classes and backbone_out_channels C % 4 == 0, 4 <= C <= 64.  Anything else
+The HIP path covers CUDA inputs with K <= 256 classes and backbone_out_channels C % 4 == 0, 4 <= C <= 128 (the 96 channels of
+SpUNet-v1m1's headless output among them).  Anything else
 (CPU tensors, other shapes), and every input under AO_AMD_CAC=torch (an A/B switch), takes a vectorised eager formulation of
 the same contract."""
 import os
@@ -33,7 +35,7 @@ from .layers import RowBatchNorm1d, RowLinear
 from .model import PointTransformerV2
 from .segmentor import _parse_criteria, cross_entropy
 
-MAX_CLASSES, MAX_CHANNELS = 256, 64
+MAX_CLASSES, MAX_CHANNELS = 256, 128
 PROTO_EPS, MEAN_EPS = 1e-7, 1e-4
 
 

@@ -807,7 +807,8 @@ int lovasz_softmax_backward_hip_launcher(int n, int c, const float *logits, cons
 /* ------------------------------------------------ context-aware classifier heads --
  * CAC-v1m1 (pointcept/models/context_aware_classifier/context_aware_classifier_v1m1_base.py) on (N, C) fp32 feature rows,
  * K classes, b scenes (`offset`: int32 cumulative row ends), max_rows = the largest scene's row count (sizes the grid; the
- * caller knows the scene bounds).  K <= 256, C % 4 == 0, 4 <= C <= 64.  No host synchronisation, no float atomics: every
+ * caller knows the scene bounds).  K <= 256, C % 4 == 0, 4 <= C <= 128 (C <= 64: cac.hip;
+ * 64 < C <= 128: cac_mfma.hip, the same contract with the products on the fp32 matrix instruction).  No host synchronisation, no float atomics: every
  * reduction goes through per-workgroup partial slabs added in a fixed order (bitwise reproducible).
  *   weighted sums (mode 0, soft prototypes): w_nk = softmax(logits_n)_k, times [max_k p_nk >= thr] when thr > 0;
  *                 z (b,K) = sum_{n in s} w_nk, out (b,K,C) = sum_{n in s} w_nk x_n / (z + eps)

@@ -3,6 +3,8 @@ step of the CAC segmentor against DefaultSegmentor with the same criteria.
 
     python tools/bench_cac.py            # every section, each in a child process under `timeout -k 10`
     python tools/bench_cac.py heads      # one section in this process
+    python tools/bench_cac.py heads --channels 96    # the heads at another backbone width (64 < C <= 128: cac_mfma.hip); such a
+                                                     # line also carries min / max ms and the allocator's peak per path
 
 Prints one JSON line per measurement.  heads: the CAC-specific work of a training step at 3 x 100 k rows, C = 48 -- soft
 prototypes, proj, feat_proj_layer (per scene and whole batch), class means, apd_proj, both cosine logits and the distillation
@@ -26,7 +28,7 @@ ROWS = [100000, 100000, 100000]
 SECTIONS = {"heads": 600, "step": 900}
 
 
-def _time(fn, iters):
+def _time(fn, iters, spread=None):
     import torch
 
     ts = []
@@ -37,6 +39,8 @@ def _time(fn, iters):
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b))
+    if spread is not None:
+        spread.update(min_ms=round(min(ts), 4), max_ms=round(max(ts), 4))
     return statistics.median(ts)
 
 
@@ -66,7 +70,7 @@ def _syncs(fn):
     return sum("synchroniz" in str(x.message) for x in w)
 
 
-def section_heads(iters):
+def section_heads(iters, channels=48):
     import torch
 
     from ao_amd.ptv2 import CACSegmentor
@@ -80,9 +84,9 @@ def section_heads(iters):
     bounds = [sum(ROWS[:i + 1]) for i in range(len(ROWS))]
     for k, thr in SIZES:
         torch.manual_seed(0)
-        seg = CACSegmentor(k, 48, backbone=Identity(), criteria=[], conf_thresh=thr, detach_pre_logits=True).cuda().train()
+        seg = CACSegmentor(k, channels, backbone=Identity(), criteria=[], conf_thresh=thr, detach_pre_logits=True).cuda().train()
         g = torch.Generator(device="cuda").manual_seed(1)
-        feat = (torch.randn(n, 48, generator=g, device="cuda") * 2).requires_grad_(True)
+        feat = (torch.randn(n, channels, generator=g, device="cuda") * 2).requires_grad_(True)
         label = torch.randint(0, k, (n,), generator=g, device="cuda")
         label[torch.rand(n, generator=g, device="cuda") < 0.1] = -1
         offset = torch.tensor(bounds, dtype=torch.int32, device="cuda")
@@ -94,13 +98,18 @@ def section_heads(iters):
             cac = seg.adaptive_logits(feat, label, bounds, offset)
             (distill_loss(refine, cac.detach(), label) + refine.mean() + cac.mean()).backward()
 
-        row = dict(rows=n, classes=k, conf_thresh=thr, channels=48)
+        row = dict(rows=n, classes=k, conf_thresh=thr, channels=channels)
         for mode in ("hip", "torch"):
             os.environ["AO_AMD_CAC"] = mode
             for _ in range(3):
                 fn()
             torch.cuda.synchronize()
-            row[mode] = dict(ms=round(_time(fn, iters), 4), launches=_launches(fn), syncs=_syncs(fn))
+            extra = {}
+            torch.cuda.reset_peak_memory_stats()
+            ms = round(_time(fn, iters, None if channels == 48 else extra), 4)
+            if channels != 48:
+                extra["peak_mb"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+            row[mode] = dict(ms=ms, launches=_launches(fn), syncs=_syncs(fn), **extra)
         row["speedup"] = round(row["torch"]["ms"] / row["hip"]["ms"], 2)
         print(json.dumps(row), flush=True)
     os.environ.pop("AO_AMD_CAC", None)
@@ -161,8 +170,16 @@ def main():
         i = args.index("--iters")
         iters = int(args[i + 1])
         del args[i:i + 2]
+    channels = 48
+    if "--channels" in args:
+        i = args.index("--channels")
+        channels = int(args[i + 1])
+        del args[i:i + 2]
     if args:
-        {"heads": section_heads, "step": section_step}[args[0]](iters)
+        if args[0] == "heads":
+            section_heads(iters, channels)
+        else:
+            section_step(iters)
         return
     for name, limit in SECTIONS.items():  # each section in a child of its own: a fault ends the run there
         rc = subprocess.call(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), name,
