@@ -221,3 +221,11 @@ if not os.path.exists(SWIN_F16_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % SWIN_F16_HEADER)
 with open(SWIN_F16_HEADER) as _f:
     swin_f16_consts, swin_f16_structs, swin_f16_signatures = parse(_f.read())
+
+# the eighteenth public header (OctFormer's dense octree convolutions: the tables between two depths, the matrix-core
+# gather-GEMM of the stem, Downsample and the decoder), likewise
+OCTCONV_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_octconv_hip.h")
+if not os.path.exists(OCTCONV_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % OCTCONV_HEADER)
+with open(OCTCONV_HEADER) as _f:
+    octconv_consts, octconv_structs, octconv_signatures = parse(_f.read())

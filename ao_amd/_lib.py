@@ -58,6 +58,8 @@ EXPECTED_SPV_ABI = 1
 EXPECTED_SWIN_ABI = 1
 # the same for include/ptv2_swin_f16_hip.h and ptv2_swin_f16_abi_version() (ao_amd/csrc/swin_attention_f16.hip)
 EXPECTED_SWIN_F16_ABI = 1
+# the same for include/ptv2_octconv_hip.h and ptv2_octconv_abi_version() (ao_amd/csrc/oct_conv.hip)
+EXPECTED_OCTCONV_ABI = 1
 
 
 def build(verbose=False):
@@ -79,7 +81,7 @@ def lib():
                       _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures, _abi.msc_signatures,
                       _abi.st_signatures, _abi.inseval_signatures, _abi.csc_signatures, _abi.v2m1_signatures,
                       _abi.spconv_bf16_signatures, _abi.oct_signatures, _abi.spv_signatures, _abi.swin_signatures,
-                      _abi.swin_f16_signatures):
+                      _abi.swin_f16_signatures, _abi.octconv_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -177,6 +179,14 @@ def lib():
         if handle.ptv2_swin_f16_struct_bytes(0) != ctypes.sizeof(_abi.swin_f16_structs["swin_f16_args"]):
             raise RuntimeError("ao_amd: swin_f16_args is %d bytes in python, %d in %s (stale build)" % (
                 ctypes.sizeof(_abi.swin_f16_structs["swin_f16_args"]), handle.ptv2_swin_f16_struct_bytes(0), LIB_PATH))
+        have = handle.ptv2_octconv_abi_version()
+        if have != EXPECTED_OCTCONV_ABI:
+            raise RuntimeError("ao_amd: %s has octconv ABI version %d, the python side expects %d -- stale build; rebuild "
+                               "with `make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_OCTCONV_ABI))
+        for which, name in enumerate(("octconv_args", "octconv_tables")):
+            if handle.ptv2_octconv_struct_bytes(which) != ctypes.sizeof(_abi.octconv_structs[name]):
+                raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (
+                    name, ctypes.sizeof(_abi.octconv_structs[name]), handle.ptv2_octconv_struct_bytes(which), LIB_PATH))
         for which, name in enumerate(("ptv1_params", "ptv1_norms", "ptv1_grads")):
             if handle.ptv2_ptv1_struct_bytes(which) != ctypes.sizeof(_abi.ptv1_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

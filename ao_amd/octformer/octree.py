@@ -81,3 +81,84 @@ def octree_level(grid_coord, batch, depth):
     run("oct_neighbors_hip_launcher", "octree_level", n=n, clouds=clouds, depth=depth, xyz=xyz, batch=bat, keys=keys,
         cloud_offsets=cloud_offsets, nbr_out=nbr)
     return OctreeLevel(order, xyz, bat, keys, cloud_offsets, nbr, clouds, depth)
+
+
+# ------------------------------------------------------------------------------------ the hierarchy ----
+TABLES = _abi.octconv_structs["octconv_tables"]
+
+
+class OctreeLink:
+    """The tables between the children (depth d, n rows) and the parents (depth d - 1, n_parent rows) of include/
+    ptv2_octconv_hip.h, all int32: `parent` (n), `child` (n_parent, 8), `onehot` (n, 8), `up` (n, 27), `down3` (n_parent, 27)."""
+
+    def __init__(self, parent, child, onehot, up, down3):
+        self.parent, self.child, self.onehot, self.up, self.down3 = parent, child, onehot, up, down3
+
+    @property
+    def n(self):
+        return self.parent.shape[0]
+
+    @property
+    def n_parent(self):
+        return self.child.shape[0]
+
+
+class OctreePyramid:
+    """`levels[i]` is the OctreeLevel of depth `depth - i`; `links[i]` the OctreeLink between levels[i] (children) and
+    levels[i + 1] (parents)."""
+
+    def __init__(self, levels, links, depth):
+        self.levels, self.links, self.depth = levels, links, depth
+
+    def level(self, depth):
+        if not self.depth - len(self.levels) < depth <= self.depth:
+            raise ValueError("ao_amd octformer: depth %d is not in this pyramid (%d .. %d)" % (depth, self.depth - len(self.levels) + 1, self.depth))
+        return self.levels[self.depth - depth]
+
+    def link(self, depth):
+        """between the children at `depth` and their parents at depth - 1"""
+        if not self.depth - len(self.levels) + 1 < depth <= self.depth:
+            raise ValueError("ao_amd octformer: no link below depth %d in this pyramid (%d .. %d)" % (depth, self.depth - len(self.levels) + 1, self.depth))
+        return self.links[self.depth - depth]
+
+
+@torch.no_grad()
+def octree_link(child, parent):
+    """The OctreeLink of two neighbouring OctreeLevels, `parent` being octree_level() of the unique coord >> 1 of `child`: in
+    (cloud, key) order the children of a node are consecutive, so one thread per parent walks them (no search); up and down3
+    go through `parent.nbr`.  Three small kernels of oct_conv.hip."""
+    n, m, dev = child.n, parent.n, child.xyz.device
+    pk = (child.batch.long() << (3 * child.depth) | child.keys) >> 3
+    first = torch.cat([pk.new_ones(1), (pk[1:] != pk[:-1]).long()]).nonzero().view(-1)
+    if first.numel() != m:
+        raise ValueError("ao_amd octformer: %d nodes at depth %d have %d parents, the level above has %d" % (n, child.depth, first.numel(), m))
+    first = torch.cat([first, first.new_full((1,), n)]).int().contiguous()
+    i32 = dict(dtype=torch.int32, device=dev)
+    link = OctreeLink(torch.empty(n, **i32), torch.empty((m, 8), **i32), torch.empty((n, 8), **i32), torch.empty((n, 27), **i32),
+                      torch.empty((m, 27), **i32))
+    a = TABLES()
+    a.n, a.n_parent = n, m
+    for name, t in (("keys", child.keys), ("xyz", child.xyz), ("first", first), ("parent_nbr", parent.nbr), ("parent", link.parent),
+                    ("child", link.child), ("onehot", link.onehot), ("up", link.up), ("down3", link.down3)):
+        setattr(a, name, t.data_ptr())
+    rc = _lib.lib().oct_conv_tables_hip_launcher(ctypes.addressof(a), _lib.stream_ptr())
+    _lib.check(rc, "oct_conv_tables_hip_launcher for octree_link")
+    return link
+
+
+@torch.no_grad()
+def octree_pyramid(grid_coord, batch, depth, levels):
+    """The OctreeLevel of every depth `depth`, depth - 1, .., depth - levels + 1 and the OctreeLink between neighbours.  Each
+    coarser level is octree_level() of the unique coord >> 1 of the level above (the first child of every run of equal parent
+    keys gives the coordinate)."""
+    depth, levels = int(depth), int(levels)
+    if not 1 <= levels <= depth:
+        raise ValueError("ao_amd octformer: %d levels from depth %d; between 1 and the depth" % (levels, depth))
+    out, links = [octree_level(grid_coord, batch, depth)], []
+    for _ in range(levels - 1):
+        child = out[-1]
+        pk = (child.batch.long() << (3 * child.depth) | child.keys) >> 3
+        head = torch.cat([pk.new_ones(1), (pk[1:] != pk[:-1]).long()]).nonzero().view(-1)
+        out.append(octree_level(child.xyz[head] >> 1, child.batch[head], child.depth - 1))
+        links.append(octree_link(child, out[-1]))
+    return OctreePyramid(out, links, depth)

@@ -8,12 +8,13 @@ the row log-sum-exp (n, H).  `octree_dwconv` is the depthwise convolution over t
 
 AO_AMD_OCTFORMER (read on every call): unset or "hip": the kernels; "torch": the reference's eager statements on the device.
 """
+import ctypes
 import os
 
 import torch
 
-from .. import _lib
-from .octree import C as CONSTS, OctreeLevel, run
+from .. import _abi, _lib
+from .octree import C as CONSTS, OctreeLevel, OctreeLink, run
 
 MAX_PATCH, MAX_HEADS, MAX_RPE, MAX_CHANNELS = (CONSTS[k] for k in ("OCT_MAX_PATCH", "OCT_MAX_HEADS", "OCT_MAX_RPE", "OCT_MAX_CHANNELS"))
 
@@ -23,6 +24,11 @@ def mode():
     if m not in ("hip", "torch"):
         raise ValueError("ao_amd octformer: AO_AMD_OCTFORMER=%r (hip or torch)" % m)
     return m
+
+
+def _wide(t):
+    """the eager path's operand: fp32, or float64 as it is (the float64 run of a whole model)"""
+    return t if t.dtype == torch.float64 else t.float()
 
 
 def pos_bnd_of(patch_size, dilation):
@@ -123,7 +129,7 @@ def octree_attention(qkv, level, table, patch_size, dilation, scale):
         raise ValueError("ao_amd octformer: %d channels per head; 16 or 32" % hd)
     if mode() == "torch":
         with torch.autocast("cuda", enabled=False):
-            return octree_attention_torch(qkv.float(), level.xyz, level.batch, level.clouds, table.float(), K, D, scale)
+            return octree_attention_torch(_wide(qkv), level.xyz, level.batch, level.clouds, _wide(table), K, D, scale)
     return _Attention.apply(qkv, table, level, K, D, scale)
 
 
@@ -173,5 +179,111 @@ def octree_dwconv(x, weights, level):
         raise ValueError("ao_amd octformer: %d channels; a multiple of 4, at most %d" % (x.shape[1], MAX_CHANNELS))
     if mode() == "torch":
         with torch.autocast("cuda", enabled=False):
-            return octree_dwconv_torch(x.float(), weights.float(), level.nbr)
+            return octree_dwconv_torch(_wide(x), _wide(weights), level.nbr)
     return _DWConv.apply(x, weights, level)
+
+
+# ----------------------------------------------------------------------- dense convolutions ----
+CONV_ARGS = _abi.octconv_structs["octconv_args"]
+CONV_MAX, CONV_STEM = (_abi.octconv_consts[k] for k in ("OCTCONV_MAX_CHANNELS", "OCTCONV_STEM_CHANNELS"))
+FORMS = ("conv3", "down2", "deconv3")
+
+
+def conv_tables(table, form):
+    """(forward table, weights read transposed, input-gradient table, its transpose flag, its reverse flag) of a form: `table`
+    is the OctreeLevel of a "conv3" (k = 3, stride 1) and the OctreeLink of a "down2" (k = 2, stride 2: children to parents)
+    or a "deconv3" (k = 3, stride 2 deconvolution: parents to children)."""
+    if form not in FORMS:
+        raise ValueError("ao_amd octformer: form %r; one of %s" % (form, ", ".join(FORMS)))
+    if not isinstance(table, OctreeLevel if form == "conv3" else OctreeLink):
+        raise TypeError("ao_amd octformer: a %s takes the %s" % (form, "OctreeLevel of its depth" if form == "conv3" else "OctreeLink above / below its depth"))
+    if form == "conv3":
+        return table.nbr, 0, table.nbr, 1, 1
+    if form == "down2":
+        return table.child, 0, table.onehot, 1, 0
+    return table.up, 1, table.down3, 0, 0
+
+
+def run_conv(launcher, **fields):
+    a = CONV_ARGS()
+    for name, value in fields.items():
+        setattr(a, name, value.data_ptr() if torch.is_tensor(value) else value)
+    rc = getattr(_lib.lib(), launcher)(ctypes.addressof(a), _lib.stream_ptr())
+    _lib.check(rc, "%s for octree_conv" % launcher)
+
+
+class _Conv(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, weights, bias, table, form, cin, cout):
+        x, w = x.contiguous(), weights.contiguous()
+        b = None if bias is None else bias.contiguous()
+        tab, transpose = conv_tables(table, form)[:2]
+        out = torch.empty((tab.shape[0], cout), dtype=torch.float32, device=x.device)
+        run_conv("oct_conv_fwd_hip_launcher", n_out=tab.shape[0], n_in=x.shape[0], slots=tab.shape[1], cin=cin, cout=cout,
+                 transpose=transpose, tab=tab, x=x, w=w, bias=_lib.ptr(b), out=out)
+        ctx.save_for_backward(x, w)
+        ctx.args = (table, form, cin, cout, b is not None)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        table, form, cin, cout, has_bias = ctx.args
+        tab, transpose, gtab, gtranspose, reverse = conv_tables(table, form)
+        g = g.contiguous()
+        g_x = g_w = g_b = None
+        if ctx.needs_input_grad[0]:
+            g_x = torch.empty_like(x)
+            run_conv("oct_conv_gx_hip_launcher", n_out=x.shape[0], n_in=g.shape[0], slots=gtab.shape[1], cin=cin, cout=cout,
+                     transpose=gtranspose, reverse=reverse, tab=gtab, x=g, w=w, out=g_x)
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            g_w = torch.empty_like(w)
+            g_b = torch.empty(cout, dtype=torch.float32, device=x.device) if has_bias else None
+            need = _lib.lib().ptv2_octconv_workspace_bytes(g.shape[0], tab.shape[1], cin, cout)
+            ws = _lib.workspace(need, x.device)
+            run_conv("oct_conv_gw_hip_launcher", n_out=g.shape[0], n_in=x.shape[0], slots=tab.shape[1], cin=cin, cout=cout,
+                     transpose=transpose, tab=tab, x=x, g=g, g_w=g_w, g_b=_lib.ptr(g_b), workspace=ws, workspace_bytes=ws.numel())
+        return g_x, g_w, g_b, None, None, None, None
+
+
+def octree_conv_torch(x, weights, bias, tab, transpose):
+    """out[i] = bias + sum_s x[tab[i, s]] W[s] (W[s] transposed with `transpose`), the slots one after the other, for any dtype"""
+    out = x.new_zeros((tab.shape[0], weights.shape[1] if transpose else weights.shape[2]))
+    for s in range(tab.shape[1]):
+        j = tab[:, s].long()
+        rows = (j >= 0).nonzero().view(-1)
+        out = out.index_add(0, rows, x[j[rows]] @ (weights[s].t() if transpose else weights[s]))
+    return out if bias is None else out + bias
+
+
+def octree_conv(x, weights, bias, table, form):
+    """The dense octree convolutions of OctFormer's stem, Downsample and decoder on ao_amd/csrc/oct_conv.hip, one autograd node:
+    form "conv3"    (n, Cout) from x (n, Cin), weights (27, Cin, Cout) and the OctreeLevel;
+    form "down2"    (n_parent, Cout) from x (n, Cin), weights (8, Cin, Cout) and the OctreeLink;
+    form "deconv3"  (n, Cout) from x (n_parent, Cin), weights (27, Cout, Cin) and the OctreeLink.
+    fp32, under autocast too.  ValueError outside Cin % 4 == 0 (or Cin <= 8), Cout % 8 == 0, both at most 384."""
+    _lib.require_cuda(x, weights, bias)
+    tab, transpose = conv_tables(table, form)[:2]
+    n_in = table.n_parent if form == "deconv3" else table.n
+    slots = tab.shape[1]
+    if x.dim() != 2 or x.shape[0] != n_in or weights.dim() != 3 or weights.shape[0] != slots or weights.shape[2 if transpose else 1] != x.shape[1]:
+        raise ValueError("ao_amd octformer: a %s takes x (%d, Cin) and weights (%d, %s); got %s %s"
+                         % (form, n_in, slots, "Cout, Cin" if transpose else "Cin, Cout", tuple(x.shape), tuple(weights.shape)))
+    cin, cout = x.shape[1], weights.shape[1 if transpose else 2]
+    if not (1 <= cin <= CONV_STEM or (cin % 4 == 0 and cin <= CONV_MAX)):
+        raise ValueError("ao_amd octformer: %d input channels; a multiple of 4 up to %d, or at most %d" % (cin, CONV_MAX, CONV_STEM))
+    if cout % 8 or not 8 <= cout <= CONV_MAX:
+        raise ValueError("ao_amd octformer: %d output channels; a multiple of 8, at most %d" % (cout, CONV_MAX))
+    if bias is not None and tuple(bias.shape) != (cout,):
+        raise ValueError("ao_amd octformer: bias is (%d,); got %s" % (cout, tuple(bias.shape)))
+    if mode() == "torch":
+        with torch.autocast("cuda", enabled=False):
+            return octree_conv_torch(_wide(x), _wide(weights), None if bias is None else _wide(bias), tab, transpose)
+    return _Conv.apply(x, weights, bias, table, form, cin, cout)
+
+
+def octree_deconv(x, weights, link):
+    """octree_conv's form "deconv3": the k = 3, stride 2 deconvolution from the parents to the children of `link`"""
+    return octree_conv(x, weights, None, link, "deconv3")

@@ -34,7 +34,7 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, H
     tester of ao_amd/ptv2/tester.py under "SemSegTester", which `test = dict(type="SemSegTester")` then resolves to.  Every
     registry may be omitted.  MODELS also receives
     CACSegmentor under "CAC-v1m1", PointTransformerV2M1 under "PT-v2m1" and Point Transformer V1 under "PointTransformer-Seg26" / "-Seg38" / "-Seg50", SpUNetBase under "SpUNet-v1m1", SPVCNN under "SPVCNN", PointGroup under "PG-v1m1", MaskedSceneContrast
-    under "MSC-v1m1", MaskedSceneContrastCSC under "MSC-v1m2" and StratifiedTransformer under "ST-v1m2" and "STv1m2"; the returned
+    under "MSC-v1m1", MaskedSceneContrastCSC under "MSC-v1m2" , StratifiedTransformer under "ST-v1m2" and "STv1m2" and OctFormer under "OctFormer-v1m1"; the returned
     list of names leaves those entries out (it predates them).  With HOOKS (pointcept/engines/hooks/builder.py) the instance
     evaluator of ao_amd/pointgroup/evaluate.py is filed under "InsSegEvaluator", likewise not listed."""
     done = []
@@ -81,6 +81,10 @@ def register(MODELS=None, OPTIMIZERS=None, force=True, LOSSES=None, TEST=None, H
 
         _register(MODELS, StratifiedTransformer, "ST-v1m2", force)
         _register(MODELS, StratifiedTransformer, "STv1m2", force)
+        # OctFormer (ao_amd/octformer), likewise filed and not listed
+        from ..octformer import OctFormer
+
+        _register(MODELS, OctFormer, "OctFormer-v1m1", force)
     if OPTIMIZERS is not None:
         from .optim import FlatAdamW
 
