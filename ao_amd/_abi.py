@@ -229,3 +229,10 @@ if not os.path.exists(OCTCONV_HEADER):
     raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % OCTCONV_HEADER)
 with open(OCTCONV_HEADER) as _f:
     octconv_consts, octconv_structs, octconv_signatures = parse(_f.read())
+
+# the nineteenth public header (OctFormer's dense octree convolutions with bf16 matrix-core operands), likewise
+OCTCONV_BF16_HEADER = os.path.join(os.path.dirname(HEADER), "ptv2_octconv_bf16_hip.h")
+if not os.path.exists(OCTCONV_BF16_HEADER):
+    raise RuntimeError("ao_amd: %s not found: the ctypes bindings are derived from it" % OCTCONV_BF16_HEADER)
+with open(OCTCONV_BF16_HEADER) as _f:
+    octconv_bf16_consts, octconv_bf16_structs, octconv_bf16_signatures = parse(_f.read())

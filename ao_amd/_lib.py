@@ -60,6 +60,8 @@ EXPECTED_SWIN_ABI = 1
 EXPECTED_SWIN_F16_ABI = 1
 # the same for include/ptv2_octconv_hip.h and ptv2_octconv_abi_version() (ao_amd/csrc/oct_conv.hip)
 EXPECTED_OCTCONV_ABI = 1
+# the same for include/ptv2_octconv_bf16_hip.h and ptv2_octconv_bf16_abi_version() (ao_amd/csrc/oct_conv_bf16.hip)
+EXPECTED_OCTCONV_BF16_ABI = 1
 
 
 def build(verbose=False):
@@ -81,7 +83,7 @@ def lib():
                       _abi.ptv1_signatures, _abi.spconv_signatures, _abi.pg_signatures, _abi.msc_signatures,
                       _abi.st_signatures, _abi.inseval_signatures, _abi.csc_signatures, _abi.v2m1_signatures,
                       _abi.spconv_bf16_signatures, _abi.oct_signatures, _abi.spv_signatures, _abi.swin_signatures,
-                      _abi.swin_f16_signatures, _abi.octconv_signatures):
+                      _abi.swin_f16_signatures, _abi.octconv_signatures, _abi.octconv_bf16_signatures):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(handle, name)
@@ -187,6 +189,12 @@ def lib():
             if handle.ptv2_octconv_struct_bytes(which) != ctypes.sizeof(_abi.octconv_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (
                     name, ctypes.sizeof(_abi.octconv_structs[name]), handle.ptv2_octconv_struct_bytes(which), LIB_PATH))
+        have = handle.ptv2_octconv_bf16_abi_version()
+        if have != EXPECTED_OCTCONV_BF16_ABI:
+            raise RuntimeError("ao_amd: %s has octconv bf16 ABI version %d, the python side expects %d -- stale build; rebuild "
+                               "with `make -C ao_amd/csrc`" % (LIB_PATH, have, EXPECTED_OCTCONV_BF16_ABI))
+        if ctypes.sizeof(_abi.octconv_bf16_structs["octconv_bf16_args"]) != ctypes.sizeof(_abi.octconv_structs["octconv_args"]):
+            raise RuntimeError("ao_amd: octconv_bf16_args and octconv_args differ in size: the two headers restate one struct")
         for which, name in enumerate(("ptv1_params", "ptv1_norms", "ptv1_grads")):
             if handle.ptv2_ptv1_struct_bytes(which) != ctypes.sizeof(_abi.ptv1_structs[name]):
                 raise RuntimeError("ao_amd: %s is %d bytes in python, %d in %s (stale build)" % (

@@ -140,3 +140,9 @@ int cac_wide_cos_backward(int b, int max_rows, int k, int c, const float *x, con
 // ---- swin_attention.hip -----------------------------------------------------------------------------------------------
 // g_X_table = the sum over the chunks' (3, R, hd) partials of a head, ascending (one launch; swin_attention_f16.hip shares it)
 int swin_table_reduce(int chunks, int R, int H, int hd, const float *part, float *gq, float *gk, float *gv, void *stream);
+// ---- oct_conv.hip -----------------------------------------------------------------------------------------------------
+// the row splits of the weight gradient of n_out rows, and what follows the splits' partials in the layout of
+// ptv2_octconv_workspace_bytes: the fixed-order finalize of g_w (more than one split) and the bias gradient (g_b not NULL);
+// oct_conv_bf16.hip writes its partials in the same layout and shares both
+int oct_conv_gw_splits(int n_out);
+int oct_conv_gw_finish(int n_out, int slots, int cin, int cout, const float *g, float *g_w, float *g_b, void *workspace, void *stream);

@@ -378,17 +378,27 @@ extern "C" int oct_conv_gw_hip_launcher(const octconv_args *args, void *stream) 
                      splits == 1 ? a.g_w : (float *)a.workspace, (size_t)elems};
     hipLaunchKernelGGL(oct_conv_gw_kernel, dim3(divup(a.cin, GCI) * divup(a.cout, GCO), a.slots, splits), dim3(TPB), 0, st, op);
     PTV2_CHECK_LAUNCH();
+    return oct_conv_gw_finish(a.n_out, a.slots, a.cin, a.cout, a.g, a.g_w, a.g_b, a.workspace, stream);
+}
+
+int oct_conv_gw_splits(int n_out) { return splits_of(n_out); }
+
+// what follows the partials of either operand form (internal.h): the splits of g_w added ascending, then the bias gradient
+int oct_conv_gw_finish(int n_out, int slots, int cin, int cout, const float *g, float *g_w, float *g_b, void *workspace, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = splits_of(n_out);
+    const long long elems = (long long)slots * cin * cout;
     if (splits > 1) {
         hipLaunchKernelGGL(oct_conv_gw_finalize_kernel, dim3(divup(elems, TPB)), dim3(TPB), 0, st, splits, elems,
-                           (const float *)a.workspace, a.g_w);
+                           (const float *)workspace, g_w);
         PTV2_CHECK_LAUNCH();
     }
-    if (a.g_b) {
-        float *strips = (float *)((char *)a.workspace + gw_partial_bytes(a.n_out, a.slots, a.cin, a.cout));
-        hipLaunchKernelGGL(oct_conv_gb_kernel, dim3(divup(a.cout, 64), GB_STRIPS), dim3(TPB), 0, st, a.n_out, a.cout,
-                           divup(divup(a.n_out, GB_STRIPS), 4) * 4, a.g, strips);
+    if (g_b) {
+        float *strips = (float *)((char *)workspace + gw_partial_bytes(n_out, slots, cin, cout));
+        hipLaunchKernelGGL(oct_conv_gb_kernel, dim3(divup(cout, 64), GB_STRIPS), dim3(TPB), 0, st, n_out, cout,
+                           divup(divup(n_out, GB_STRIPS), 4) * 4, g, strips);
         PTV2_CHECK_LAUNCH();
-        hipLaunchKernelGGL(oct_conv_gb_finalize_kernel, dim3(divup(a.cout, TPB)), dim3(TPB), 0, st, a.cout, (const float *)strips, a.g_b);
+        hipLaunchKernelGGL(oct_conv_gb_finalize_kernel, dim3(divup(cout, TPB)), dim3(TPB), 0, st, cout, (const float *)strips, g_b);
         PTV2_CHECK_LAUNCH();
     }
     return PTV2_OK;

@@ -13,7 +13,7 @@ import torch
 from torch.utils.checkpoint import checkpoint
 
 from .octree import octree_pyramid
-from .ops import octree_attention, octree_conv, octree_dwconv, pos_bnd_of
+from .ops import OPERANDS, octree_attention, octree_conv, octree_dwconv, pos_bnd_of
 
 
 class MLP(torch.nn.Module):
@@ -181,6 +181,7 @@ class OctreeConv(torch.nn.Module):
     """ocnn.nn.OctreeConv for kernel_size [3] with stride 1 and [2] with stride 2; `weights` (kdim, Cin, Cout) and `bias` are
     ocnn's shapes and keys, restated from its documentation (unpinned)"""
     transposed = False
+    operands = "fp32"   # of octree_conv; PatchEmbed, Downsample and OctFormerDecoder set it from their conv_operands
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: List[int] = [3], stride: int = 1, nempty: bool = False,
                  direct_method: bool = False, use_bias: bool = False, max_buffer: int = int(2e8)):
@@ -198,7 +199,7 @@ class OctreeConv(torch.nn.Module):
 
     def forward(self, data: torch.Tensor, octree, depth: int):
         table = octree.level(depth) if self.form == "conv3" else octree.link(depth if self.form == "down2" else depth + 1)
-        return octree_conv(data, self.weights, self.bias, table, self.form)
+        return octree_conv(data, self.weights, self.bias, table, self.form, self.operands)
 
     def extra_repr(self) -> str:
         return "in_channels={}, out_channels={}, kernel_size={}, stride={}, bias={}".format(
@@ -208,6 +209,15 @@ class OctreeConv(torch.nn.Module):
 class OctreeDeconv(OctreeConv):
     """ocnn.nn.OctreeDeconv for kernel_size [3], stride 2: depth -> depth + 1; `weights` (27, Cout, Cin)"""
     transposed = True
+
+
+def _set_conv_operands(module, conv_operands):
+    """hands `conv_operands` ("fp32", "bf16" or "autocast") to every octree convolution below `module`"""
+    if conv_operands not in OPERANDS:
+        raise ValueError("ao_amd octformer: conv_operands must be one of %s, got %r" % (", ".join(map(repr, OPERANDS)), conv_operands))
+    for m in module.modules():
+        if isinstance(m, OctreeConv):
+            m.operands = conv_operands
 
 
 class OctreeConvBnRelu(torch.nn.Module):
@@ -253,7 +263,7 @@ class OctreeUpsample(torch.nn.Module):
 
 
 class OctFormerDecoder(torch.nn.Module):
-    def __init__(self, channels: List[int], fpn_channel: int, nempty: bool, head_up: int = 1):
+    def __init__(self, channels: List[int], fpn_channel: int, nempty: bool, head_up: int = 1, conv_operands: str = "fp32"):
         super().__init__()
         self.head_up = head_up
         self.num_stages = len(channels)
@@ -263,6 +273,7 @@ class OctFormerDecoder(torch.nn.Module):
                                             for _ in range(self.num_stages)])
         self.up_conv = torch.nn.ModuleList([OctreeDeconvBnRelu(fpn_channel, fpn_channel, kernel_size=[3], stride=2, nempty=nempty)
                                             for _ in range(self.head_up)])
+        _set_conv_operands(self, conv_operands)
 
     def forward(self, features, octree):
         depth = min(features.keys())
@@ -284,7 +295,8 @@ class OctFormerDecoder(torch.nn.Module):
 
 
 class PatchEmbed(torch.nn.Module):
-    def __init__(self, in_channels: int = 3, dim: int = 96, num_down: int = 2, nempty: bool = True, **kwargs):
+    def __init__(self, in_channels: int = 3, dim: int = 96, num_down: int = 2, nempty: bool = True, conv_operands: str = "fp32",
+                 **kwargs):
         super().__init__()
         self.num_stages = num_down
         self.delta_depth = -num_down
@@ -294,6 +306,7 @@ class PatchEmbed(torch.nn.Module):
         self.downsamples = torch.nn.ModuleList([OctreeConvBnRelu(channels[i], channels[i + 1], kernel_size=[2], stride=2, nempty=nempty)
                                                 for i in range(self.num_stages)])
         self.proj = OctreeConvBnRelu(channels[-1], dim, kernel_size=[3], stride=1, nempty=nempty)
+        _set_conv_operands(self, conv_operands)
 
     def forward(self, data: torch.Tensor, octree, depth: int):
         for i in range(self.num_stages):
@@ -304,10 +317,12 @@ class PatchEmbed(torch.nn.Module):
 
 
 class Downsample(torch.nn.Module):
-    def __init__(self, in_channels: int, out_channels: int, kernel_size: List[int] = (2,), nempty: bool = True):
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: List[int] = (2,), nempty: bool = True,
+                 conv_operands: str = "fp32"):
         super().__init__()
         self.norm = torch.nn.BatchNorm1d(out_channels)
         self.conv = OctreeConv(in_channels, out_channels, kernel_size, stride=2, nempty=nempty, use_bias=True)
+        _set_conv_operands(self, conv_operands)
 
     def forward(self, data: torch.Tensor, octree, depth: int):
         return self.norm(self.conv(data, octree, depth))
@@ -319,11 +334,13 @@ class OctFormer(torch.nn.Module):
     floor((coord / octree_scale_factor + 1) * 2^(octree_depth - 1)), one torch.unique gives the leaves and the point -> leaf
     inverse, a leaf's feature is the mean of `feat` over its points, and OctreeInterp("nearest") is the leaf's row of each
     point.  No full layers are built: the coarsest depth in use must lie above octree_full_depth.  `normal` takes no part (the
-    reference's patch_embed reads octree.features alone)."""
+    reference's patch_embed reads octree.features alone).
+    conv_operands ("fp32", "bf16" or "autocast"; not a reference argument) is octree_conv's `operands` for every convolution of
+    patch_embed, downsamples and decoder; the stem layers (Cin <= 8) keep their fp32 kernel."""
 
     def __init__(self, in_channels, num_classes, fpn_channels=168, channels=(96, 192, 384, 384), num_blocks=(2, 2, 18, 2),
                  num_heads=(6, 12, 24, 24), patch_size=26, stem_down=2, head_up=2, dilation=4, drop_path=0.5, nempty=True,
-                 octree_scale_factor=10.24, octree_depth=11, octree_full_depth=2):
+                 octree_scale_factor=10.24, octree_depth=11, octree_full_depth=2, conv_operands="fp32"):
         super().__init__()
         _nempty(nempty)
         self.patch_size = patch_size
@@ -341,15 +358,17 @@ class OctFormer(torch.nn.Module):
             raise ValueError("ao_amd octformer: head_up %d != stem_down %d: the decoder must end at the leaves" % (head_up, stem_down))
         drop_ratio = torch.linspace(0, drop_path, sum(num_blocks)).tolist()
 
-        self.patch_embed = PatchEmbed(in_channels, channels[0], stem_down, nempty)
+        self.patch_embed = PatchEmbed(in_channels, channels[0], stem_down, nempty, conv_operands=conv_operands)
         self.layers = torch.nn.ModuleList([
             OctFormerStage(dim=channels[i], num_heads=num_heads[i], patch_size=patch_size,
                            drop_path=drop_ratio[sum(num_blocks[:i]): sum(num_blocks[: i + 1])], dilation=dilation, nempty=nempty,
                            num_blocks=num_blocks[i])
             for i in range(self.num_stages)])
-        self.downsamples = torch.nn.ModuleList([Downsample(channels[i], channels[i + 1], kernel_size=[2], nempty=nempty)
+        self.downsamples = torch.nn.ModuleList([Downsample(channels[i], channels[i + 1], kernel_size=[2], nempty=nempty,
+                                                           conv_operands=conv_operands)
                                                 for i in range(self.num_stages - 1)])
-        self.decoder = OctFormerDecoder(channels=channels, fpn_channel=fpn_channels, nempty=nempty, head_up=head_up)
+        self.decoder = OctFormerDecoder(channels=channels, fpn_channel=fpn_channels, nempty=nempty, head_up=head_up,
+                                        conv_operands=conv_operands)
         self.seg_head = (torch.nn.Sequential(torch.nn.Linear(fpn_channels, fpn_channels), torch.nn.BatchNorm1d(fpn_channels),
                                              torch.nn.ReLU(inplace=True), torch.nn.Linear(fpn_channels, num_classes))
                          if num_classes > 0 else torch.nn.Identity())

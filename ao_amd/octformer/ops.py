@@ -185,8 +185,10 @@ def octree_dwconv(x, weights, level):
 
 # ----------------------------------------------------------------------- dense convolutions ----
 CONV_ARGS = _abi.octconv_structs["octconv_args"]
+CONV_BF16_ARGS = _abi.octconv_bf16_structs["octconv_bf16_args"]   # the same fields (include/ptv2_octconv_bf16_hip.h)
 CONV_MAX, CONV_STEM = (_abi.octconv_consts[k] for k in ("OCTCONV_MAX_CHANNELS", "OCTCONV_STEM_CHANNELS"))
 FORMS = ("conv3", "down2", "deconv3")
+OPERANDS = ("fp32", "bf16", "autocast")
 
 
 def conv_tables(table, form):
@@ -204,8 +206,10 @@ def conv_tables(table, form):
     return table.up, 1, table.down3, 0, 0
 
 
-def run_conv(launcher, **fields):
-    a = CONV_ARGS()
+def run_conv(launcher, bf16=False, **fields):
+    """`launcher` is "fwd", "gx" or "gw": of oct_conv.hip, or with bf16 operands of oct_conv_bf16.hip"""
+    launcher = "oct_conv_%s%s_hip_launcher" % ("bf16_" if bf16 else "", launcher)
+    a = (CONV_BF16_ARGS if bf16 else CONV_ARGS)()
     for name, value in fields.items():
         setattr(a, name, value.data_ptr() if torch.is_tensor(value) else value)
     rc = getattr(_lib.lib(), launcher)(ctypes.addressof(a), _lib.stream_ptr())
@@ -215,37 +219,38 @@ def run_conv(launcher, **fields):
 class _Conv(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, x, weights, bias, table, form, cin, cout):
+    def forward(ctx, x, weights, bias, table, form, cin, cout, bf16):
         x, w = x.contiguous(), weights.contiguous()
         b = None if bias is None else bias.contiguous()
         tab, transpose = conv_tables(table, form)[:2]
         out = torch.empty((tab.shape[0], cout), dtype=torch.float32, device=x.device)
-        run_conv("oct_conv_fwd_hip_launcher", n_out=tab.shape[0], n_in=x.shape[0], slots=tab.shape[1], cin=cin, cout=cout,
+        run_conv("fwd", bf16, n_out=tab.shape[0], n_in=x.shape[0], slots=tab.shape[1], cin=cin, cout=cout,
                  transpose=transpose, tab=tab, x=x, w=w, bias=_lib.ptr(b), out=out)
         ctx.save_for_backward(x, w)
-        ctx.args = (table, form, cin, cout, b is not None)
+        ctx.args = (table, form, cin, cout, b is not None, bf16)
         return out
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        table, form, cin, cout, has_bias = ctx.args
+        table, form, cin, cout, has_bias, bf16 = ctx.args
         tab, transpose, gtab, gtranspose, reverse = conv_tables(table, form)
         g = g.contiguous()
         g_x = g_w = g_b = None
         if ctx.needs_input_grad[0]:
             g_x = torch.empty_like(x)
-            run_conv("oct_conv_gx_hip_launcher", n_out=x.shape[0], n_in=g.shape[0], slots=gtab.shape[1], cin=cin, cout=cout,
+            run_conv("gx", bf16, n_out=x.shape[0], n_in=g.shape[0], slots=gtab.shape[1], cin=cin, cout=cout,
                      transpose=gtranspose, reverse=reverse, tab=gtab, x=g, w=w, out=g_x)
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             g_w = torch.empty_like(w)
             g_b = torch.empty(cout, dtype=torch.float32, device=x.device) if has_bias else None
-            need = _lib.lib().ptv2_octconv_workspace_bytes(g.shape[0], tab.shape[1], cin, cout)
+            L = _lib.lib()
+            need = (L.ptv2_octconv_bf16_workspace_bytes if bf16 else L.ptv2_octconv_workspace_bytes)(g.shape[0], tab.shape[1], cin, cout)
             ws = _lib.workspace(need, x.device)
-            run_conv("oct_conv_gw_hip_launcher", n_out=g.shape[0], n_in=x.shape[0], slots=tab.shape[1], cin=cin, cout=cout,
+            run_conv("gw", bf16, n_out=g.shape[0], n_in=x.shape[0], slots=tab.shape[1], cin=cin, cout=cout,
                      transpose=transpose, tab=tab, x=x, g=g, g_w=g_w, g_b=_lib.ptr(g_b), workspace=ws, workspace_bytes=ws.numel())
-        return g_x, g_w, g_b, None, None, None, None
+        return g_x, g_w, g_b, None, None, None, None, None
 
 
 def octree_conv_torch(x, weights, bias, tab, transpose):
@@ -258,13 +263,37 @@ def octree_conv_torch(x, weights, bias, tab, transpose):
     return out if bias is None else out + bias
 
 
-def octree_conv(x, weights, bias, table, form):
+class _RoundBf16(torch.autograd.Function):
+    """x rounded to the nearest bf16 value, kept in its dtype; the gradient passes as it is"""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.bfloat16().to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+def _bf16_operands(operands):
+    """Decided at the call, before .apply: custom_fwd turns autocast off inside the node."""
+    if operands not in OPERANDS:
+        raise ValueError("ao_amd octformer: operands must be one of %s, got %r" % (", ".join(map(repr, OPERANDS)), operands))
+    return operands == "bf16" or (operands == "autocast" and torch.is_autocast_enabled("cuda"))
+
+
+def octree_conv(x, weights, bias, table, form, operands="fp32"):
     """The dense octree convolutions of OctFormer's stem, Downsample and decoder on ao_amd/csrc/oct_conv.hip, one autograd node:
     form "conv3"    (n, Cout) from x (n, Cin), weights (27, Cin, Cout) and the OctreeLevel;
     form "down2"    (n_parent, Cout) from x (n, Cin), weights (8, Cin, Cout) and the OctreeLink;
     form "deconv3"  (n, Cout) from x (n_parent, Cin), weights (27, Cout, Cin) and the OctreeLink.
-    fp32, under autocast too.  ValueError outside Cin % 4 == 0 (or Cin <= 8), Cout % 8 == 0, both at most 384."""
+    fp32, under autocast too.  ValueError outside Cin % 4 == 0 (or Cin <= 8), Cout % 8 == 0, both at most 384.
+    operands: "fp32" is that path whatever autocast says; "bf16" runs ao_amd/csrc/oct_conv_bf16.hip (x, W and the output's
+    gradient rounded to bf16 on their way into the matrix core; accumulation, bias and everything in memory fp32); "autocast" is
+    bf16 exactly when CUDA autocast is on at the call.  A stem layer (Cin <= 8) keeps the fp32 kernel whatever it says.  The
+    eager path rounds x and W through bf16 (straight-through gradient; g is not rounded there) unless they are float64."""
     _lib.require_cuda(x, weights, bias)
+    bf16 = _bf16_operands(operands)
     tab, transpose = conv_tables(table, form)[:2]
     n_in = table.n_parent if form == "deconv3" else table.n
     slots = tab.shape[1]
@@ -278,12 +307,16 @@ def octree_conv(x, weights, bias, table, form):
         raise ValueError("ao_amd octformer: %d output channels; a multiple of 8, at most %d" % (cout, CONV_MAX))
     if bias is not None and tuple(bias.shape) != (cout,):
         raise ValueError("ao_amd octformer: bias is (%d,); got %s" % (cout, tuple(bias.shape)))
+    bf16 = bf16 and cin > CONV_STEM
     if mode() == "torch":
         with torch.autocast("cuda", enabled=False):
-            return octree_conv_torch(_wide(x), _wide(weights), None if bias is None else _wide(bias), tab, transpose)
-    return _Conv.apply(x, weights, bias, table, form, cin, cout)
+            x, weights = _wide(x), _wide(weights)
+            if bf16 and x.dtype != torch.float64:
+                x, weights = _RoundBf16.apply(x), _RoundBf16.apply(weights)
+            return octree_conv_torch(x, weights, None if bias is None else _wide(bias), tab, transpose)
+    return _Conv.apply(x, weights, bias, table, form, cin, cout, bf16)
 
 
-def octree_deconv(x, weights, link):
+def octree_deconv(x, weights, link, operands="fp32"):
     """octree_conv's form "deconv3": the k = 3, stride 2 deconvolution from the parents to the children of `link`"""
-    return octree_conv(x, weights, None, link, "deconv3")
+    return octree_conv(x, weights, None, link, "deconv3", operands)
